@@ -4,6 +4,11 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: the ranks are spawned by this process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1, external launcher)
+    python bench.py ... --dump-outputs DIR                        (+ the flows of the last timed step as DIR/*.npy)
+    python bench.py ... --full                                     (+ power, clock, kernel table, rooflines, CPU baseline, EPE, ...)
+
+A plain run sets up, warms up, times K steps and prints the headline JSON line; everything else the record can hold is
+measured with --full only, after the timed steps.
 
 A "step" = one full pass of the hot path over one clip per rank: corr volumes + pyramids for the 3 pairs,
 context split, GMA attention matrix, 15 refinement iterations (lookup, motion encoder, aggregate, temporal
@@ -152,6 +157,35 @@ def timed_steps(step_fn, steps: int, warmup: int, world: int, sync_fn, barrier_f
     barrier_fn()
     dt = time.perf_counter() - t0
     return allreduce_max_fn(dt)
+
+
+DUMP_BYTES = 48_000_000
+
+
+def dump_outputs(outs, out_dir: str, budget_bytes: int = DUMP_BYTES):
+    """--dump-outputs: the flows a caller of the timed path receives from one step, `outs` = the (flows_up, flows_lowres) of each
+    forward of that step, as out_dir/flow_up_<pair>.npy [clips, 2, 8h, 8w] and flow_low_<pair>.npy [clips, 2, h, w] in float32
+    (the clips of all forwards of the step concatenated).  At most `budget_bytes` of data in all: the smallest arrays are written
+    whole, and an array that does not fit its share of the rest is replaced by a sample of its flattened elements, at indices
+    drawn from a fixed seed (the same in every run with the same arguments, so that two builds compare element for element).
+    Returns the names written."""
+    import numpy as np
+    arrays = {}
+    for i in range(len(outs[0][0])):
+        arrays[f"flow_up_{i}"] = torch.cat([o[0][i] for o in outs])
+        arrays[f"flow_low_{i}"] = torch.cat([o[1][i] for o in outs])
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget_bytes // 4
+    names = sorted(arrays, key=lambda k: arrays[k].numel())
+    for k, name in enumerate(names):
+        x = arrays[name].detach().to("cpu", torch.float32)
+        share = left // (len(names) - k)
+        if x.numel() > share:
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            x = x.reshape(-1)[idx]
+        left -= x.numel()
+        np.save(os.path.join(out_dir, name + ".npy"), x.numpy())
+    return names
 
 
 class PowerSampler:
@@ -538,10 +572,24 @@ def main():
     ap.add_argument("--corr-layout", default="blocked", choices=["blocked", "rows"],
                     help="fp32 volumes (--corr-only and the fp32_class engine): cache-line blocks (csrc/corr_blocked32.hip) or the "
                          "reference's row-major maps with line-aligned row pitches (csrc/corr.hip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also measure everything else of the JSON record: package power, the sustained "
+                         "clock, the per-kernel table and rooflines, the CPU oracle baseline and EPE checks, the other presets, the "
+                         "single-clip latency and frames -> flows (a plain run times the steps and prints the headline line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the flows the last timed step returned as DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of the larger fields, at most 48 MB in all) to compare two builds output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline and the EPE checks")
     ap.add_argument("--cpu-runs", type=int, default=3, help="timed whole-clip runs of the CPU oracle (median reported)")
-    ap.add_argument("--no-kernel-breakdown", action="store_true")
+    ap.add_argument("--no-kernel-breakdown", action="store_true",
+                    help="--full: skip the clock probe, the per-kernel table, the other presets, single clip and frames -> flows")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.corr_only:
+        ap.error("--dump-outputs writes the flows of the hot path; --corr-only has none")
+    if not args.full:
+        args.no_kernel_breakdown = args.no_cpu_baseline = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -567,7 +615,7 @@ def main():
     if "SF_BENCH_DEVICE" in os.environ and not args.share_device:
         local_rank = int(os.environ["SF_BENCH_DEVICE"])
     # (first power reading = the idle draw: before this process touches the GPU)
-    power = PowerSampler() if (world == 1 and not args.corr_only) else None
+    power = PowerSampler() if (world == 1 and not args.corr_only and args.full) else None
     assert torch.cuda.is_available(), "bench.py needs MI355X GPUs"
     if args.share_device:
         local_rank %= torch.cuda.device_count()
@@ -628,6 +676,8 @@ def main():
         args.no_kernel_breakdown = args.no_cpu_baseline = True          # (the N = 1 weak-scaling line carries those)
         assert args.streams == 1, "--total-clips and --streams exclude each other"
 
+    # what the forwards of the latest step returned (views into engine buffers; --dump-outputs reads them after the timed steps)
+    last = []
     if args.streams > 1:
         assert B % args.streams == 0, "--clips must be a multiple of --streams"
         args.no_kernel_breakdown = args.no_cpu_baseline = True
@@ -638,22 +688,23 @@ def main():
 
         def step():
             cur = torch.cuda.current_stream()
+            outs = []
             for e, st, (f, c) in zip(engs, strs, parts):
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
-                    e.forward(f, c, iters=iters, all_masks=args.all_masks)
+                    outs.append(e.forward(f, c, iters=iters, all_masks=args.all_masks))
             for st in strs:
                 cur.wait_stream(st)
+            last[:] = outs
     elif strong:
         # one input set per distinct launch size (the same synthetic clips every launch: timing does not depend on the values)
         feats = {b: (fmaps[:b].contiguous(), cnets[:b].contiguous()) for b in set(my_batches)}
 
         def step():
-            for b in my_batches:
-                eng.forward(*feats[b], iters=iters, all_masks=args.all_masks)
+            last[:] = [eng.forward(*feats[b], iters=iters, all_masks=args.all_masks) for b in my_batches]
     else:
         def step():
-            eng.forward(fmaps, cnets, iters=iters, all_masks=args.all_masks)
+            last[:] = [eng.forward(fmaps, cnets, iters=iters, all_masks=args.all_masks)]
 
     def barrier():
         if world > 1:
@@ -677,6 +728,9 @@ def main():
     if power is not None:
         power.on = False
     log(f"timed region: {args.steps} steps in {dt:.3f}s (this rank: {own[0]:.3f}s)")
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on these engines: their returned flows are views into buffers the next forward overwrites
+        log(f"outputs of the last timed step: {', '.join(dump_outputs(last, args.dump_outputs))} -> {args.dump_outputs}")
     per_rank, rank_cores, rank_host, rank_host_cpu = [own[0]], [len(RANK_CPUS)], [own[1]], [own[2]]
     pl0 = next(reversed(eng._plans.values())) if eng._plans else None
     graph_calls = [int(getattr(pl0, "graph_calls", 0) or 0)]

@@ -991,7 +991,7 @@ def test_warm_start_clip_loop_vs_oracle(dev):
 
 @pytest.mark.gpu
 def test_bench_contract_line(dev):
-    """bench.py prints ONE JSON line with the driver's contract fields plus `roofline` and `cpu_baseline`
+    """bench.py --full prints ONE JSON line with the driver's contract fields plus `roofline` and `cpu_baseline`
     (a reduced run: demo256 workload, 2 clips, 2 steps)."""
     import json
     import os
@@ -999,7 +999,7 @@ def test_bench_contract_line(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--workload", "demo256", "--clips", "2"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--workload", "demo256", "--clips", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -1016,6 +1016,35 @@ def test_bench_contract_line(dev):
     c = d["roofline"]["clock"]
     assert 500.0 < c["sustained_mhz"] <= 2600.0 and 500.0 < c["idle_probe_mhz"] <= 2600.0 and len(c["reads_mhz"]) == 4
 
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(dev, tmp_path):
+    """A plain bench.py run (no --full) prints the headline line alone, and --dump-outputs writes the flows its last timed step
+    returned: float32, whole where they fit, the same bits in a second run with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--workload", "demo256", "--clips", "2", "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        runs.append(json.loads(lines[0]))
+    for d in runs:
+        assert d["metric"] == "flow_fields_per_sec" and d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert not {"roofline", "cpu_baseline", "kernels", "epe_vs_oracle", "single_clip"} & set(d) and d["power"] is None
+    for i in range(3):                                          # demo256: T = 4 -> 3 pairs, 32 x 32 grid, 2 clips
+        for kind, shape in (("up", (2, 2, 256, 256)), ("low", (2, 2, 32, 32))):
+            a = np.load(tmp_path / "a" / f"flow_{kind}_{i}.npy")
+            b = np.load(tmp_path / "b" / f"flow_{kind}_{i}.npy")
+            assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all() and np.abs(a).max() > 0
+            assert np.array_equal(a, b)
 
 @pytest.mark.gpu
 def test_clock_probe_branch_leaves_the_results_alone(dev):

@@ -38,8 +38,12 @@ def test_corr_pyramid_and_lookup(golden, tag):
     pyr = orc.corr_pyramid(f1, f2)
     for i, lvl in enumerate(pyr):
         close(lvl, g[f"level{i}"], 2e-6, 1e-6)
-    # level 0 is the same matmul -> expect bit equality with the reference here
-    assert np.array_equal(pyr[0].numpy(), g["level0"])
+    # level 0 is the same matmul as the reference's (corr.py:46-54: f1^T f2, then / sqrt of D as a float32 tensor) -> expect bit
+    # equality with that formula evaluated HERE.  Not with the golden bits: the CPU BLAS picks its kernel by the host's instruction
+    # set, and the order of its sums, so the volume's last bits differ between hosts (the golden is pinned by `close` above).
+    B, D, h, w = f1.shape
+    ref0 = torch.matmul(f1.view(B, D, h * w).transpose(1, 2), f2.view(B, D, h * w)) / torch.sqrt(torch.tensor(D).float())
+    assert np.array_equal(pyr[0].numpy(), ref0.reshape(pyr[0].shape).numpy())
     close(orc.corr_lookup(pyr, coords), g["lookup"], 5e-6)
     close(orc.corr_lookup(pyr, ident), g["lookup_identity"], 5e-6)
 

@@ -4,8 +4,8 @@ cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05f; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -4
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -3
-timeout 900 python bench.py > $O/r05_bench_default.json 2> $O/bench_default.err; tail -c 400 $O/r05_bench_default.json; echo
-N="--no-cpu-baseline"
+timeout 900 python bench.py --full > $O/r05_bench_default.json 2> $O/bench_default.err; tail -c 400 $O/r05_bench_default.json; echo
+N="--full --no-cpu-baseline"
 timeout 300 python bench.py $N --workload kitti > $O/r05_bench_kitti.json 2>/dev/null
 timeout 300 python bench.py $N --workload spring --clips 1 > $O/r05_bench_spring.json 2>/dev/null
 timeout 300 python bench.py $N --clips 1 > $O/r05_bench_clip1.json 2>/dev/null

@@ -6,8 +6,8 @@ O=gpurun_out/r06f; mkdir -p $O
 cp gpurun_out/r06p/r06_traffic_*.json gpurun_out/r06p/r06_mfma_busy_*.json profiles/ 2>/dev/null
 timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -4
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -3
-timeout 900 python bench.py > $O/r06_bench_default.json 2> $O/bench_default.err; tail -c 400 $O/r06_bench_default.json; echo
-N="--no-cpu-baseline"
+timeout 900 python bench.py --full > $O/r06_bench_default.json 2> $O/bench_default.err; tail -c 400 $O/r06_bench_default.json; echo
+N="--full --no-cpu-baseline"
 timeout 300 python bench.py $N --workload kitti > $O/r06_bench_kitti.json 2>/dev/null
 timeout 300 python bench.py $N --workload spring --clips 1 > $O/r06_bench_spring.json 2>/dev/null
 timeout 300 python bench.py $N --clips 1 > $O/r06_bench_clip1.json 2>/dev/null
