@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 121
+#define SF_VERSION 122
 
 enum {
     SF_OK = 0,
@@ -562,6 +562,23 @@ int sf_upsample_flow(const float* flow, const float* mask, float* out, int n, in
  * remaining point (exact Euclidean nearest neighbour in float64, lowest source index on ties), zero if none is left.
  * Replaces scipy.interpolate.griddata(method='nearest') on the host. */
 int sf_forward_interpolate(const float* flow, float* out, int n_img, int h, int w, void* stream);
+
+/* ---- tiled inference: Gaussian-weighted blend of overlapping crops (evaluate_mf.py:985-1053, :919-982) ----------------
+ * flows [n_clips * n_distinct][pairs][2][tile_h][tile_w] (the per-crop upsampled flows), weights [tile_h][tile_w] (one crop's
+ * Gaussian patch), out [n_clips][pairs][2][out_h][out_w] = the window (out_y0, out_x0) of the img_h x img_w canvas.  Per pixel,
+ * over the entries k of the crop sequence (origins tile_y/x[k], distinct crop tile_id[k]; duplicates included) that cover it and
+ * in that order: acc = acc + f * w, wsum = wsum + w; out = acc / wsum -- each operation rounded on its own in fp32, subnormals
+ * kept (bitwise the reference's F.pad accumulation on the CPU). */
+#define SF_TILE_MAX 64
+typedef struct SfTilePlan {
+    int32_t n_seq, n_distinct;
+    int32_t tile_h, tile_w;
+    int32_t img_h, img_w;
+    int32_t out_y0, out_x0, out_h, out_w;
+    int32_t tile_y[SF_TILE_MAX], tile_x[SF_TILE_MAX], tile_id[SF_TILE_MAX];
+} SfTilePlan;
+int sf_tile_blend(const float* flows, const float* weights, float* out, const SfTilePlan* plan, int n_clips, int pairs,
+                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,15 @@ class SfMaskUpsample(C.Structure):
     ]
 
 
+class SfTilePlan(C.Structure):
+    _fields_ = [
+        ("n_seq", C.c_int32), ("n_distinct", C.c_int32), ("tile_h", C.c_int32), ("tile_w", C.c_int32),
+        ("img_h", C.c_int32), ("img_w", C.c_int32), ("out_y0", C.c_int32), ("out_x0", C.c_int32),
+        ("out_h", C.c_int32), ("out_w", C.c_int32),
+        ("tile_y", C.c_int32 * 64), ("tile_x", C.c_int32 * 64), ("tile_id", C.c_int32 * 64),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol of include/streamflow_hip.h
 SIGNATURES = {
     "sf_version": (_i, []),
@@ -160,6 +169,7 @@ SIGNATURES = {
     "sf_dwconv3x3_res": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sf_upsample_flow": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_forward_interpolate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "sf_tile_blend": (_i, [_vp, _vp, _vp, C.POINTER(SfTilePlan), _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

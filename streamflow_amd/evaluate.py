@@ -10,11 +10,14 @@
   ``multi_root/training/image_2/000NNN_FF.png`` + ``flow_occ/000NNN_10.png``: the clip is frames 12 - nframes .. 11, only the
   LAST pair (frames 10 -> 11) has ground truth (core/mf_datasets.py:946-952); 'kitti' padding; EPE and the F1-all outlier rate
   (epe > 3 px and epe / |gt| > 5 %) over pixels with valid >= 0.5; returns ``{'kitti_epe': .., 'kitti_f1': ..}``.
+* ``validate_kitti_mf_tile(model, iters, multi_root, nframes)`` / ``validate_kitti_tile(model, iters, root)`` -- the tiled KITTI
+  protocols (evaluate_mf.py:985-1053 / :919-982): fixed-height bottom padding, overlapping crops of the training size, crops
+  blended with a Gaussian weight each (streamflow_amd.tiling, the sf_tile_blend kernel); same scoring.
 
 ``model`` is anything with the reference's test-mode call ``model(images: list of [1,3,H,W] in 0..255, iters=.., test_mode=True)
 -> list of nframes - 1 flows [1,2,H,W]`` (streamflow_amd.SKFlow_MF8, or the CPU oracle wrapped the same way in the tests).
-Files are read with this package's own codecs (flow_io.py: PNG, .flo, KITTI 16-bit PNG).  Host-side plumbing: nothing here
-launches a kernel itself.
+Files are read with this package's own codecs (flow_io.py: PNG, .flo, KITTI 16-bit PNG).  Host-side plumbing: the only kernel
+launched here is the tile blend of the tiled validators (ops.tile_blend) for models without ``forward_tiled``.
 """
 from __future__ import annotations
 
@@ -135,3 +138,103 @@ def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str]
     f1 = float(100 * np.mean(np.concatenate(out_list)))
     print("Validation KITTI: %f, %f" % (epe, f1))
     return {"kitti_epe": epe, "kitti_f1": f1}
+
+
+# ---- tiled inference (evaluate_mf.py:858-1053) ------------------------------------------------------------------------------
+def _tiled_flows(model: Callable, images: List[torch.Tensor], padder, tile: Tuple[int, int], iters: Optional[int],
+                 dev: torch.device) -> List[torch.Tensor]:
+    """Blended flows [2, h, w] (padding removed) of one clip of padded frames [1,3,Hp,Wp].  A model with `forward_tiled` runs all
+    its crops in one batch; any other model (the CPU oracle, a stub) is called once per DISTINCT crop with the reference's
+    test-mode call and the crops are blended by the same HIP kernel on `dev`.  `iters=None`: the model's own default (the
+    reference's validate_kitti_tile calls the model without iters)."""
+    from . import ops, tiling
+    kw = {} if iters is None else {"iters": iters}
+    if hasattr(model, "forward_tiled"):
+        flows = model.forward_tiled(images, tile=tile, sigma=tiling.TILE_SIGMA, min_overlap=20, **kw)
+        return [padder.unpad(f[0]).float() for f in flows]
+    plan = tiling.make_plan(images[0].shape[-2:], tile, 20, pad=padder._pad)
+    crops = []
+    for (y, x) in plan.distinct:
+        pred = model([im[:, :, y:y + tile[0], x:x + tile[1]] for im in images], test_mode=True, **kw)
+        crops.append(torch.stack([f[0].float().to(dev) for f in pred]))
+    out = ops.tile_blend(torch.stack(crops).contiguous(), tiling.tile_weights(tile, tiling.TILE_SIGMA, dev), plan)
+    return [out[0, i] for i in range(out.shape[1])]
+
+
+def _kitti_scores(pairs) -> Tuple[float, float]:
+    """Mean of the per-frame EPE and the F1-all rate (epe > 3 px and > 5 % of |gt|) over pixels with valid >= 0.5, the
+    reference's scoring of every KITTI validator; `pairs` yields (flow [2,H,W], gt [2,H,W], valid [H,W]) on the host."""
+    out_list, epe_list = [], []
+    for flow, gt, valid in pairs:
+        epe = torch.sum((flow - gt) ** 2, dim=0).sqrt().view(-1)
+        mag = torch.sum(gt ** 2, dim=0).sqrt().view(-1)
+        val = valid.view(-1) >= 0.5
+        out = ((epe > 3.0) & ((epe / mag) > 0.05)).float()
+        epe_list.append(epe[val].mean().item())
+        out_list.append(out[val].numpy())
+    epe = float(np.mean(np.array(epe_list)))
+    f1 = float(100 * np.mean(np.concatenate(out_list)))
+    print("Validation KITTI: %f, %f" % (epe, f1))
+    return epe, f1
+
+
+def _kitti_gt(path: str):
+    gt_np, valid_np = flow_io.read_flow_kitti(path)
+    return torch.from_numpy(gt_np).permute(2, 0, 1).float(), torch.from_numpy(valid_np)
+
+
+@torch.no_grad()
+def validate_kitti_mf_tile(model: Callable, iters: int = 6, multi_root: Optional[str] = None, nframes: int = 3,
+                           device: Optional[torch.device] = None) -> Dict[str, float]:
+    """The reference's tiled multi-frame KITTI protocol (evaluate_mf.py:985-1053): the clip of validate_kitti_mf, replicate-padded
+    at the bottom to 432 rows, cut into 432 x 960 crops (the grid follows the frame width: KITTI has 1242, 1241, 1238, 1226 and
+    1224), blended with sigma = 0.05; scored on the last pair.  Returns {'kitti_epe', 'kitti_f1'}."""
+    from .tiling import KITTI_MF_TILE, FixedHeightPadder
+    if multi_root is None:
+        raise ValueError("validate_kitti_mf_tile: multi_root (the multi-frame KITTI-2015 tree) is required")
+    dev = device or _device_of(model)
+    image_root = os.path.join(multi_root, "training", "image_2")
+    flow_root = os.path.join(multi_root, "training", "flow_occ")
+    seqs = sorted(os.path.basename(p)[:6] for p in glob.glob(os.path.join(flow_root, "??????_10.png")))
+    if not seqs:
+        raise RuntimeError(f"no ground truth under {flow_root}")
+
+    def pairs():
+        for seq in seqs:
+            images = [_image(os.path.join(image_root, "%s_%02d.png" % (seq, i)))[None].to(dev) for i in range(12 - nframes, 12)]
+            padder = FixedHeightPadder(images[0].shape, KITTI_MF_TILE[0], mode="replicate")
+            flows = _tiled_flows(model, padder.pad_list(images), padder, KITTI_MF_TILE, iters, dev)
+            gt, valid = _kitti_gt(os.path.join(flow_root, seq + "_10.png"))
+            yield flows[nframes - 2].cpu(), gt, valid                      # only the last pair (frames 10 -> 11) has ground truth
+
+    epe, f1 = _kitti_scores(pairs())
+    return {"kitti_epe": epe, "kitti_f1": f1}
+
+
+@torch.no_grad()
+def validate_kitti_tile(model: Callable, iters: int = 6, root: Optional[str] = None,
+                        device: Optional[torch.device] = None) -> Dict[str, float]:
+    """The reference's tiled two-frame KITTI protocol (evaluate_mf.py:919-982) over ``root/training/image_2/*_10.png``,
+    ``*_11.png`` and ``flow_occ/*_10.png`` (core/datasets.py:229-245): zero-padded at the bottom to 376 rows, 376 x 720 crops,
+    sigma = 0.05.  As in the reference, the model is called WITHOUT `iters` (its own default applies; `iters` is accepted and
+    ignored) and needs T = 2.  Returns {'kitti-epe', 'kitti-f1'} (the reference's hyphenated keys)."""
+    from .tiling import KITTI_TILE, FixedHeightPadder
+    if root is None:
+        raise ValueError("validate_kitti_tile: root (the KITTI-2015 tree) is required")
+    dev = device or _device_of(model)
+    images1 = sorted(glob.glob(os.path.join(root, "training", "image_2", "*_10.png")))
+    images2 = sorted(glob.glob(os.path.join(root, "training", "image_2", "*_11.png")))
+    flows_gt = sorted(glob.glob(os.path.join(root, "training", "flow_occ", "*_10.png")))
+    if not flows_gt or len(images1) != len(flows_gt) or len(images2) != len(flows_gt):
+        raise RuntimeError(f"{root}: {len(images1)} / {len(images2)} frame pairs for {len(flows_gt)} ground-truth files")
+
+    def pairs():
+        for im1, im2, fl in zip(images1, images2, flows_gt):
+            images = [_image(p)[None].to(dev) for p in (im1, im2)]
+            padder = FixedHeightPadder(images[0].shape, KITTI_TILE[0], mode="zeros")
+            flows = _tiled_flows(model, padder.pad(*images), padder, KITTI_TILE, None, dev)
+            gt, valid = _kitti_gt(fl)
+            yield flows[-1].cpu(), gt, valid
+
+    epe, f1 = _kitti_scores(pairs())
+    return {"kitti-epe": epe, "kitti-f1": f1}

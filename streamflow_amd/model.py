@@ -114,6 +114,42 @@ class SKFlow_MF8(nn.Module):
         imgs = 2 * (imgs / 255.0) - 1.0
         return self._forward_normalised(imgs, iters, flow_init, test_mode)
 
+    @torch.no_grad()
+    def forward_tiled(self, images: Sequence[torch.Tensor], iters: int = 12, tile=(432, 960), sigma: float = 0.05,
+                      min_overlap: int = 20, flow_init=None) -> List[torch.Tensor]:
+        """Tiled inference (the reference's KITTI tile protocol, evaluate_mf.py:985-1053) on frames of any size >= `tile`: the
+        frames are cut into overlapping crops of `tile` (tiling.tile_grid), the model runs on every crop and the crops' flows are
+        blended with a Gaussian weight per crop (`sigma`).  Same input convention as `forward`; returns T-1 flows [B,2,H,W].
+        Each distinct crop runs once (the reference's crop sequence lists every KITTI crop twice): the distinct crops of all B
+        clips are one batch of B * n_distinct clips through the encoders and the engine (one graph with use_graph), then one
+        sf_tile_blend launch adds the crops in the reference's order, duplicates included."""
+        return self._forward_tiled_normalised(self._normalise(images), iters, tile, sigma, min_overlap, flow_init)
+
+    def _normalise(self, images) -> torch.Tensor:
+        imgs = torch.stack(list(images), dim=1)
+        return 2 * (imgs / 255.0) - 1.0
+
+    def _forward_tiled_normalised(self, imgs: torch.Tensor, iters: int, tile, sigma: float, min_overlap: int, flow_init):
+        from . import ops, tiling
+        if flow_init is not None:
+            raise NotImplementedError("forward_tiled: a warm start (flow_init) is not supported with tiled inference")
+        B, T, C, H, W = imgs.shape
+        th, tw = int(tile[0]), int(tile[1])
+        if th % 8 or tw % 8:
+            raise RuntimeError(f"tile {th} x {tw}: both sides must be multiples of 8")
+        plan = tiling.make_plan((H, W), (th, tw), min_overlap)
+        nd = plan.n_distinct
+        # clip-major batch of the distinct crops (indexing only: the crops are the values of the whole frame)
+        crops = torch.stack(plan.crops(imgs), dim=1).reshape(B * nd, T, C, th, tw).contiguous()
+        fmaps, cnets = self._features(crops)
+        ups, _ = self.engine(imgs.device).forward(fmaps, cnets, iters=iters)
+        P = T - 1
+        flows = ups[0].as_strided((B * nd, P, 2, th, tw), (P * 2 * th * tw, 2 * th * tw, th * tw, tw, 1))
+        if P > 1 and ups[1].data_ptr() - ups[0].data_ptr() != 4 * 2 * th * tw:
+            raise RuntimeError("forward_tiled: unexpected layout of the engine's upsampled flows")
+        out = ops.tile_blend(flows, tiling.tile_weights((th, tw), sigma, imgs.device), plan, n_clips=B)
+        return [out[:, i] for i in range(P)]
+
     def _forward_normalised(self, imgs: torch.Tensor, iters: int, flow_init, test_mode: bool):
         B, T, C, H, W = imgs.shape
         if H % 8 or W % 8:
@@ -160,3 +196,12 @@ class StreamFlowT4(SKFlow_MF8):
     def forward(self, images: torch.Tensor, iters: int = 15, flow_init=None, upsample: bool = True,
                 test_mode: bool = True):
         return self._forward_normalised(images, iters, flow_init, test_mode)
+
+    def _normalise(self, images) -> torch.Tensor:
+        return images
+
+    @torch.no_grad()
+    def forward_tiled(self, images: torch.Tensor, iters: int = 15, tile=(432, 960), sigma: float = 0.05, min_overlap: int = 20,
+                      flow_init=None) -> List[torch.Tensor]:
+        """SKFlow_MF8.forward_tiled with this class's input convention (images [B,T,3,H,W] in [-1,1], iters=15)."""
+        return self._forward_tiled_normalised(self._normalise(images), iters, tile, sigma, min_overlap, flow_init)

@@ -1177,6 +1177,33 @@ def forward_interpolate(flow: torch.Tensor) -> torch.Tensor:
     return out
 
 
+@on_tensor_device
+def tile_blend(flows: torch.Tensor, weights: torch.Tensor, plan, n_clips: int = 1) -> torch.Tensor:
+    """Gaussian-weighted blend of tiled inference (reference evaluate_mf.py:1021-1035): flows [n_clips * n_distinct, pairs, 2, th, tw]
+    (the distinct crops of every clip, clip-major), weights [th, tw] (tiling.tile_weights), plan a tiling.TilePlan ->
+    [n_clips, pairs, 2, h, w] over plan.crop, bitwise the reference's fp32 accumulation over plan.sequence."""
+    _dev_check(flows)
+    _dev_check(weights)
+    th, tw = plan.tile_hw
+    nd = plan.n_distinct
+    if flows.dim() != 5 or flows.shape[0] != n_clips * nd or flows.shape[2:] != (2, th, tw):
+        raise RuntimeError(f"tile_blend: flows {tuple(flows.shape)} do not match {n_clips} clip(s) x {nd} crop(s) of {th} x {tw}")
+    if tuple(weights.shape) != (th, tw) or weights.device != flows.device:
+        raise RuntimeError(f"tile_blend: weights {tuple(weights.shape)} on {weights.device} for crops of {th} x {tw} on {flows.device}")
+    pairs = int(flows.shape[1])
+    y0, x0, h, w = plan.crop
+    desc = _lib.SfTilePlan(n_seq=len(plan.sequence), n_distinct=nd, tile_h=th, tile_w=tw, img_h=plan.image_hw[0],
+                           img_w=plan.image_hw[1], out_y0=y0, out_x0=x0, out_h=h, out_w=w)
+    if len(plan.sequence) > len(desc.tile_y):
+        raise RuntimeError(f"tile_blend: {len(plan.sequence)} crops exceed the limit of {len(desc.tile_y)}")
+    for k, ((ty, tx), d) in enumerate(zip(plan.sequence, plan.index)):
+        desc.tile_y[k], desc.tile_x[k], desc.tile_id[k] = ty, tx, d
+    out = torch.empty(n_clips, pairs, 2, h, w, dtype=torch.float32, device=flows.device)
+    _lib.check(_lib.load().sf_tile_blend(flows.data_ptr(), weights.data_ptr(), out.data_ptr(), C.byref(desc), n_clips, pairs,
+                                         _lib.stream()), "sf_tile_blend")
+    return out
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None
