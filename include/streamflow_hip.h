@@ -222,12 +222,14 @@ typedef struct SfGemm {
     const void* A_hi; const void* A_lo;   /* SF_LAYOUT_SPLIT_F16 operand (shared by all batch indices) */
     int64_t lda_h;                /* rows per k-octet plane of A_hi/A_lo (M padded to 128) */
     int32_t a_padded;             /* K_MAJOR fp32 A is zero padded to [K up to 32][M up to 128]: no bounds checks */
-    /* split-K (precision F16X3 only): the K range is cut into k_splits slices, slice s writes its partial
-       product (epilogue must be SF_EPI_NONE, no bias) to C + s*split_stride; combine with sf_splitk_combine. */
+    /* split-K (the split precisions F16X3 / F16X2 / F16; refused in FP32): the K range is cut into k_splits <= 16 slices of
+       whole k-tiles, slice s writes its partial product (epilogue must be SF_EPI_NONE, no bias) to C + s*split_stride;
+       combine with sf_splitk_combine. */
     int32_t k_splits; int64_t split_stride;
     /* optional scratch (caller-owned).  If given (>= auto_split_max * batch * M * N floats... see sf_gemm_split_ws_floats)
-       and k_splits == 0, the library may split K on its own for small grids with deep K (F16X3 only): partial
-       products go to the scratch and a second kernel applies bias / epilogue.  Results are deterministic. */
+       and k_splits == 0, the library may split K on its own for small grids with deep K (split precisions only; FP32 ignores
+       the scratch, and so do conv3x3, c_f16, r_f16 and problems the activation-stationary kernel takes): partial products
+       go to the scratch and a second kernel applies bias / epilogue.  Results are deterministic. */
     float* split_ws; int64_t split_ws_floats;
     /* c_f16 = 1 (split precisions, 16-byte-aligned C, N % 4 == 0, ldc % 4 == 0): C points to IEEE fp16 storage, results are
        rounded to nearest and stored as halves (ldc, strideC in halves): the K-major fp16 operand of the next sf_gemm.

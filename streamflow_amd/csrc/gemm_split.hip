@@ -601,7 +601,9 @@ int pick_tile(const SplitArgs& a, hipStream_t st) {
 }
 
 int64_t span_bytes(int layout, int X, int K, int64_t ld, int group, int64_t group_stride) {
-    if (layout == SF_LAYOUT_F16_K_MINOR) return ((int64_t)(X - 1) * ld + K) * 2;
+    // (whole dwords: the buffer range check zeroes a dword that reaches past the range, and with an odd K the last half of the
+    // last row shares its dword with the half after it -- which lies in the same aligned dword, and is zeroed in store())
+    if (layout == SF_LAYOUT_F16_K_MINOR) return ((int64_t)(X - 1) * ld + K + 1) / 2 * 4;
     if (layout == SF_LAYOUT_F16_K_MAJOR) return ((int64_t)(K - 1) * ld + X) * 2;
     if (layout == SF_LAYOUT_SPLIT_KOCT) return (int64_t)((K + 7) / 8) * ld * 16 * 2;
     if (layout == SF_LAYOUT_F16_KOCT)
@@ -716,7 +718,7 @@ int check_output_formats(const SfGemm& g) {
 
 namespace sf {
 
-// called from sf_gemm (gemm.hip) when precision == SF_PRECISION_F16X3 (never for conv3x3)
+// sf_gemm_split_ws_floats (gemm.hip); the scratch is used by gemm_split_dispatch, i.e. in every split precision (never for conv3x3)
 int64_t gemm_split_ws_floats(int M, int N, int K, int batch) {
     const int ks = auto_splits(M, N, K, batch);
     return ks > 1 ? (int64_t)ks * batch * M * N : 0;

@@ -128,7 +128,7 @@ struct Operand {
         for (int j = 0; j < NI; ++j) {
             if (LAY == SF_LAYOUT_F16_K_MINOR) {
                 // already fp16: k0 rides in the VGPR offset so that the range check sees it (reads past the end give 0;
-                // the tail k >= K inside a row reads the next row's finite values against zeroed A columns)
+                // the tail k >= K inside a row reads the row's padding or the next row, zeroed in store())
                 rg.ph[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[j] + k0 * 2, 0, 0);
             } else if (LAY == 2) {
                 rg.ph[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[j], (k0 / 8) * ld * 16, 0);
@@ -171,6 +171,14 @@ struct Operand {
         for (int j = 0; j < NI; ++j) {
             if (!live[j]) continue;
             if (LAY == SF_LAYOUT_F16_K_MINOR) {
+                if (k0 + BK > K) {          // last, partial k-tile (workgroup-uniform): k >= K read the row's padding, which
+                                            // may hold anything (NaN * the zeroed A column is NaN) -- force it to zero
+                    f16x8 h = __builtin_bit_cast(f16x8, rg.ph[j]);
+                    const int k = k0 + ko[j] * 8;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) h[i] = (k + i < K) ? h[i] : (_Float16)0.f;
+                    rg.ph[j] = __builtin_bit_cast(u32x4, h);
+                }
                 *reinterpret_cast<u32x4*>(lds_hi + lds_off[j]) = rg.ph[j];
             } else if (LAY == 2) {
                 *reinterpret_cast<u32x4*>(lds_hi + lds_off[j]) = rg.ph[j];
