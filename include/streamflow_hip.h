@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 122
+#define SF_VERSION 123
 
 enum {
     SF_OK = 0,
@@ -581,6 +581,28 @@ typedef struct SfTilePlan {
 } SfTilePlan;
 int sf_tile_blend(const float* flows, const float* weights, float* out, const SfTilePlan* plan, int n_clips, int pairs,
                   void* stream);
+
+/* ---- flow colour-wheel images (core/utils/flow_viz.py: flow_to_image; demo.py vis_flow, the submission writers) --------
+ * flows [n][2][h][w] fp32 (ch0 = u, ch1 = v) -> out [n][h][w][3] uint8 (RGB, or BGR with bgr != 0), the Middlebury wheel of
+ * Baker et al. with 55 entries.  Every field is normalised by its OWN maximum radius (written to rad_max_ws[n], which stays
+ * readable after the call), or by fixed_rad_max when that is >= 0 (rad_max_ws may then be null and no reduction is launched).
+ * At most two kernels and one memset on `stream`, no host synchronisation: safe inside graph capture.
+ *
+ * Arithmetic (the reference's numpy arithmetic for float32 input, except for its libm's float32 arctan2):
+ *   fp32, every operation rounded on its own, subnormals kept, correctly rounded division and square root:
+ *     [clip_flow >= 0: u, v clamped to [0, clip_flow] first -- np.clip(flow, 0, clip_flow): NEGATIVE components become 0]
+ *     rad = sqrt(u u + v v), m = max over the field, d = m + 1e-5f, u' = u / d, v' = v / d, rad' = sqrt(u' u' + v' v')
+ *     angle = fp32(atan2(-(double)v', -(double)u'))   (the fp64 arctangent rounded once; the negation keeps the sign of zero:
+ *             v = +0, u > 0 gives -pi = wheel entry 0, v = -0 gives +pi = entry 54)
+ *     a = angle / (float)pi, fk = (a + 1) / 2 * 54, k0 = floor(fk), k1 = k0 + 1 (55 -> 0)
+ *   fp64 (numpy's float32 - int32 is float64): f = fk - k0 (exact), c0 = wheel[k0] / 255, c1 = wheel[k1] / 255,
+ *     col = (1 - f) c0 + f c1,
+ *     col = rad' <= 1 ? 1 - rad' (1 - col) : col * 0.75   (the second branch is reachable with fixed_rad_max only),
+ *     byte = floor(255 col).
+ * A pixel with a non-finite component does not enter the maximum and is painted (0, 0, 0) (the reference is undefined there);
+ * an all-zero field is white.  Limits: n, h, w > 0, h * w < 2^30, n <= 65535. */
+int sf_flow_to_image(const float* flows, uint8_t* out, float* rad_max_ws, int n, int h, int w, float clip_flow,
+                     float fixed_rad_max, int bgr, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-"""Clip grouping of the reference's demo pipeline (demo.py:502-534), without its video I/O (decord / cv2).
+"""Clip grouping of the reference's demo pipeline (demo.py:502-534) and its `vis_flow` (demo.py:536-548), without its video I/O
+(decord / cv2): frames come in as tensors and the colour-wheel images leave as a PNG sequence.
 
 The demo slides a window of T frames with stride T-1 over the video; the last window re-uses the final T frames
 and drops the flow fields that an earlier window already produced (``flags == -1``).  Every consecutive frame pair
@@ -69,3 +70,37 @@ def predict_clips_warm_start(model: Callable, clips: Sequence[Sequence[torch.Ten
         flow_prev = [forward_interpolate(l[0])[None] for l in lowres]
         out.append(flows)
     return out
+
+
+def colour_images(flows: Sequence[torch.Tensor], rad_max=None) -> List:
+    """numpy uint8 [H, W, 3] colour-wheel images of device flows [2, H, W] (or [1, 2, H, W]), in order.  Fields of equal shape
+    are stacked and coloured by ONE ops.flow_to_image call (each still on its own scale unless `rad_max` fixes one)."""
+    from . import ops
+    fields = [f[0] if f.dim() == 4 else f for f in flows]
+    images: List = [None] * len(fields)
+    by_shape = {}
+    for i, f in enumerate(fields):
+        by_shape.setdefault((tuple(f.shape), f.device), []).append(i)
+    for idx in by_shape.values():
+        batch = torch.stack([fields[i].detach().float() for i in idx]).contiguous()
+        if not batch.is_cuda and torch.cuda.is_available():
+            batch = batch.to(torch.device("cuda", torch.cuda.current_device()))
+        out = ops.flow_to_image(batch, rad_max=rad_max).cpu().numpy()
+        for k, i in enumerate(idx):
+            images[i] = out[k]
+    return images
+
+
+def vis_flow(flows_result: Sequence[torch.Tensor], save_dir: str = "flow_result", rad_max=None) -> List[str]:
+    """The reference's `vis_flow` (demo.py:536-548) with a PNG sequence ``save_dir/frame_%04d.png`` in place of its mp4 (no video
+    encoder here).  flows_result: flow fields [2, H, W] as `predict_frames` returns them (CPU tensors are moved to the current
+    GPU: the colouring is the sf_flow_to_image kernel, all fields of equal shape in one call).  `rad_max` fixes one scale for the
+    whole sequence (no flicker between frames); default: each frame on its own scale, as the reference.  Returns the paths."""
+    import os
+    from . import flow_io
+    os.makedirs(save_dir, exist_ok=True)
+    paths = []
+    for i, img in enumerate(colour_images(flows_result, rad_max=rad_max)):
+        paths.append(os.path.join(save_dir, "frame_%04d.png" % i))
+        flow_io.write_png(paths[-1], img)
+    return paths

@@ -1204,6 +1204,30 @@ def tile_blend(flows: torch.Tensor, weights: torch.Tensor, plan, n_clips: int = 
     return out
 
 
+@on_tensor_device
+def flow_to_image(flows: torch.Tensor, clip_flow: Optional[float] = None, rad_max: Optional[float] = None,
+                  convert_to_bgr: bool = False, return_rad_max: bool = False):
+    """Middlebury colour-wheel images of flow fields (reference core/utils/flow_viz.py: flow_to_image): flows [N, 2, H, W] ->
+    uint8 [N, H, W, 3] on the same device, all N fields in one sf_flow_to_image call, each normalised by its OWN largest radius
+    (or all by `rad_max` when given: one scale for a whole video, values above it are drawn at 0.75 brightness).  `clip_flow`
+    clamps both components to [0, clip_flow] first, as the reference's np.clip does (a quirk: negative components become 0).
+    A pixel with a non-finite component is black and does not enter the maximum.  return_rad_max: also the fp32 maxima [N]
+    (None with a fixed `rad_max`)."""
+    _dev_check(flows)
+    if flows.dim() != 4 or flows.shape[1] != 2 or flows.numel() == 0:
+        raise RuntimeError(f"flow_to_image: expected flows [N, 2, H, W], got {tuple(flows.shape)}")
+    if (clip_flow is not None and not clip_flow >= 0) or (rad_max is not None and not rad_max >= 0):
+        raise RuntimeError(f"flow_to_image: clip_flow / rad_max must be >= 0 (got {clip_flow}, {rad_max})")
+    n, _, h, w = flows.shape
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=flows.device)
+    ws = torch.empty(n, dtype=torch.float32, device=flows.device) if rad_max is None else None
+    _lib.check(_lib.load().sf_flow_to_image(flows.data_ptr(), out.data_ptr(), None if ws is None else ws.data_ptr(), n, h, w,
+                                            -1.0 if clip_flow is None else float(clip_flow),
+                                            -1.0 if rad_max is None else float(rad_max), int(bool(convert_to_bgr)), _lib.stream()),
+               "sf_flow_to_image")
+    return (out, ws) if return_rad_max else out
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None

@@ -1,0 +1,126 @@
+"""Leaderboard writers with the reference's signatures and file names (SURVEY.md row f3's last step).
+
+* ``create_sintel_submission_mf(args, model, iters, output_path, nframes)`` -- reference evaluate_mf.py:252-282 over
+  ``args.sintel_root/test/{clean,final}/<scene>/*.png``: the clip schedule of ``evaluate.sintel_clip_schedule``, pad -> model ->
+  unpad, and for every pair whose frame id is not -1 the flow as ``output_path/<dstype>/<scene>/frame%04d.flo`` (id + 1) and its
+  colour-wheel image as ``output_path/<dstype>/<scene>-<id + 1>.png``.
+* ``create_sintel_submission_mf_warmup`` -- evaluate_mf.py:286-323: the same, every clip warm-started from the previous clip's
+  low-resolution flows (``demo.predict_clips_warm_start``, one chain per scene).
+* ``create_kitti_submission_mf(args, model, iters, output_path, nframes, vis_path)`` -- submit_mf.py:700-728 over
+  ``args.multi_root/testing/image_2/000NNN_FF.png``, frames 12 - nframes .. 11, the padder in its default ('sintel') mode as the
+  reference has it there, the LAST flow as the 16-bit PNG ``output_path/000NNN_10.png``; the colour image goes to
+  ``vis_path/flow/000NNN_10.png`` when `vis_path` is given (the reference always writes ``vis_kitti2/`` into the working directory).
+
+``model`` is the reference's test-mode call (see evaluate.py).  The colour images of one clip are made on the device by ONE
+``ops.flow_to_image`` call before the flows are copied to the host; ``vis=False`` launches no kernel, which lets the writers run
+with a CPU model.
+"""
+from __future__ import annotations
+
+import glob
+import os
+from typing import Callable, List, Optional
+
+import torch
+
+from . import flow_io
+from .evaluate import _device_of, _image, _scenes, sintel_clip_schedule
+from .utils import InputPadder
+
+
+def _eval_mode(model) -> None:
+    if hasattr(model, "eval"):
+        model.eval()
+
+
+def _colour(flows: List[torch.Tensor], keep: List[int]) -> dict:
+    """{pair index: uint8 [H, W, 3]} of the kept pairs of one clip: one kernel call on the device flows."""
+    from . import ops
+    if not keep:
+        return {}
+    imgs = ops.flow_to_image(torch.stack([flows[i].float() for i in keep]).contiguous()).cpu().numpy()
+    return {i: imgs[k] for k, i in enumerate(keep)}
+
+
+def _write_sintel_clip(flows: List[torch.Tensor], ids: List[int], output_path: str, dstype: str, scene: str, vis: bool) -> None:
+    """flows: nframes - 1 unpadded fields [2, H, W]; ids: the clip's frame ids (-1: pair already written by an earlier clip)."""
+    assert len(flows) == len(ids) - 1
+    output_dir = os.path.join(output_path, dstype, scene)
+    os.makedirs(output_dir, exist_ok=True)
+    keep = [i for i in range(len(flows)) if ids[i] != -1]
+    images = _colour(flows, keep) if vis else {}
+    for i in keep:
+        flow_io.write_flo(os.path.join(output_dir, "frame%04d.flo" % (ids[i] + 1)), flows[i].permute(1, 2, 0).float().cpu().numpy())
+        if vis:
+            flow_io.write_png(os.path.join(output_path, dstype, "%s-%d.png" % (scene, ids[i] + 1)), images[i])
+
+
+def _sintel_scenes(args, dstype: str, nframes: int):
+    """(scene, sorted frame paths, clip schedule) of every scene of the test split."""
+    image_root = os.path.join(args.sintel_root, "test", dstype)
+    for scene in _scenes(image_root):
+        imgs = sorted(glob.glob(os.path.join(image_root, scene, "*.png")))
+        yield scene, imgs, sintel_clip_schedule(len(imgs), nframes)
+
+
+@torch.no_grad()
+def create_sintel_submission_mf(args, model: Callable, iters: int, output_path: str = "sintel_submission", nframes: int = 3,
+                                vis: bool = True, device: Optional[torch.device] = None) -> None:
+    """Create the submission tree for the Sintel leaderboard (every clip from a cold start)."""
+    _eval_mode(model)
+    dev = device or _device_of(model)
+    for dstype in ("clean", "final"):
+        for scene, imgs, schedule in _sintel_scenes(args, dstype, nframes):
+            for first, ids in schedule:
+                images = [_image(p)[None].to(dev) for p in imgs[first:first + nframes]]
+                padder = InputPadder(images[0].shape)
+                flows = model(padder.pad_list(images), iters=iters, test_mode=True)
+                _write_sintel_clip([padder.unpad(f[0]) for f in flows], ids, output_path, dstype, scene, vis)
+
+
+@torch.no_grad()
+def create_sintel_submission_mf_warmup(args, model: Callable, iters: int, output_path: str = "sintel_submission",
+                                       nframes: int = 3, vis: bool = True, device: Optional[torch.device] = None) -> None:
+    """Create the submission tree for the Sintel leaderboard with the warm-start chain: inside a scene every clip starts from the
+    previous clip's low-resolution flows pushed forward along themselves; the chain restarts with every scene (the reference's
+    `flow_prev = None`, which `demo.predict_clips_warm_start` spells as zero flows so that the model also returns the
+    low-resolution fields).  Clips are read one at a time; the files of a scene are written when its chain is done."""
+    from .demo import predict_clips_warm_start
+    _eval_mode(model)
+    dev = device or _device_of(model)
+    for dstype in ("clean", "final"):
+        for scene, imgs, schedule in _sintel_scenes(args, dstype, nframes):
+            padder = InputPadder(flow_io.read_png(imgs[0]).shape[:2])
+
+            def clips():
+                for first, _ in schedule:
+                    yield padder.pad_list([_image(p)[None].to(dev) for p in imgs[first:first + nframes]])
+
+            for (_, ids), flows in zip(schedule, predict_clips_warm_start(model, clips(), iters=iters)):
+                _write_sintel_clip([padder.unpad(f[0]) for f in flows], ids, output_path, dstype, scene, vis)
+
+
+@torch.no_grad()
+def create_kitti_submission_mf(args, model: Callable, iters: int, output_path: str = "kitti_submission", nframes: int = 3,
+                               vis_path: Optional[str] = None, device: Optional[torch.device] = None) -> None:
+    """Create the submission folder for the KITTI-2015 leaderboard from the multi-frame test split: one 16-bit PNG per sequence
+    (the flow of frames 10 -> 11).  Sequences are those present under ``testing/image_2`` (the reference walks 000000 .. 000199)."""
+    _eval_mode(model)
+    dev = device or _device_of(model)
+    image_root = os.path.join(args.multi_root, "testing", "image_2")
+    seqs = sorted(os.path.basename(p)[:6] for p in glob.glob(os.path.join(image_root, "??????_10.png")))
+    if not seqs:
+        raise RuntimeError(f"no sequences under {image_root}")
+    os.makedirs(output_path, exist_ok=True)
+    if vis_path is not None:
+        os.makedirs(os.path.join(vis_path, "flow"), exist_ok=True)
+    for seq in seqs:
+        images = [_image(os.path.join(image_root, "%s_%02d.png" % (seq, i)))[None].to(dev) for i in range(12 - nframes, 12)]
+        padder = InputPadder(images[0].shape)                    # default mode, as submit_mf.py:711 (not 'kitti')
+        flows = model(padder.pad_list(images), iters=iters, test_mode=True)
+        flow = padder.unpad(flows[-1][0])
+        frame_name = seq + "_10.png"
+        image = _colour([flow], [0])[0] if vis_path is not None else None
+        flow_io.write_flow_kitti(os.path.join(output_path, frame_name), flow.permute(1, 2, 0).float().cpu().numpy())
+        if image is not None:
+            flow_io.write_png(os.path.join(vis_path, "flow", frame_name), image)
