@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 123
+#define SF_VERSION 124
 
 enum {
     SF_OK = 0,
@@ -603,6 +603,33 @@ int sf_tile_blend(const float* flows, const float* weights, float* out, const Sf
  * an all-zero field is white.  Limits: n, h, w > 0, h * w < 2^30, n <= 65535. */
 int sf_flow_to_image(const float* flows, uint8_t* out, float* rad_max_ws, int n, int h, int w, float clip_flow,
                      float fixed_rad_max, int bgr, void* stream);
+
+/* ---- Spring scoring (evaluate_mf.py:50-102 validate_spring_mf) -----------------------------------------------------------
+ * Scores one predicted field against one ground-truth field and ADDS the result into acc[SF_SCORE_LEN] (fp64, on the device).
+ *   pred: fp32 planes [2][h][w]: u at pred[y * pred_row_stride + x], v at the same + pred_ch_stride (a view into a padded output
+ *         needs no copy).
+ *   gt:   fp32 interleaved [gt_h][gt_w][2] (read_flo5's array); pixel (y, x) is scored against gt[step * y][step * x], step = 1
+ *         or 2 (2 = the reference's flow[::2, ::2], mf_datasets.py:189-190); gt_h > step (h - 1), gt_w > step (w - 1).
+ *   ws:   scratch of SF_SCORE_WS_BYTES bytes (per-block partials); it is not read by later calls.
+ * Per pixel, fp32 with every operation rounded on its own (no contraction; correctly rounded square root):
+ *   e = sqrt((pu - gu)(pu - gu) + (pv - gv)(pv - gv)),  valid = !isnan(gu + gv),  mag = sqrt(gu gu + gv gv).
+ * Entries (counts are exact in fp64 below 2^53; NaN compares false):
+ *   PIXELS         pixels                       SUM_EPE        sum of e (fp64; NaN if any e is NaN)
+ *   LT1 / LT3 / LT5  pixels with e < 1 / 3 / 5    GT1            pixels with e > 1
+ *   VALID          valid pixels                 SUM_EPE_VALID  sum of e over valid pixels
+ *   S0_10, S0_10_GT1     valid & mag < 10,          and of those e > 1
+ *   S10_40, S10_40_GT1   valid & 10 <= mag < 40,    and of those e > 1
+ *   S40, S40_GT1         valid & mag >= 40,         and of those e > 1
+ * Deterministic: per-block partials summed in a fixed order by a second one-block kernel, no atomics; repeated calls give bitwise
+ * equal accumulators.  Two kernels on `stream`, no host synchronisation.  Limits: h, w > 0, h * w < 2^30. */
+enum {
+    SF_SCORE_PIXELS = 0, SF_SCORE_SUM_EPE = 1, SF_SCORE_LT1 = 2, SF_SCORE_LT3 = 3, SF_SCORE_LT5 = 4, SF_SCORE_GT1 = 5,
+    SF_SCORE_VALID = 6, SF_SCORE_SUM_EPE_VALID = 7, SF_SCORE_S0_10 = 8, SF_SCORE_S0_10_GT1 = 9, SF_SCORE_S10_40 = 10,
+    SF_SCORE_S10_40_GT1 = 11, SF_SCORE_S40 = 12, SF_SCORE_S40_GT1 = 13, SF_SCORE_LEN = 14
+};
+#define SF_SCORE_WS_BYTES (1024 * SF_SCORE_LEN * 8)
+int sf_flow_score(const float* pred, int64_t pred_ch_stride, int64_t pred_row_stride, const float* gt, int gt_h, int gt_w,
+                  int step, int h, int w, double* acc, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -171,6 +171,7 @@ SIGNATURES = {
     "sf_forward_interpolate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sf_tile_blend": (_i, [_vp, _vp, _vp, C.POINTER(SfTilePlan), _i, _i, _vp]),
     "sf_flow_to_image": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
+    "sf_flow_score": (_i, [_vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

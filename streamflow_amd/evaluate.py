@@ -13,11 +13,16 @@
 * ``validate_kitti_mf_tile(model, iters, multi_root, nframes)`` / ``validate_kitti_tile(model, iters, root)`` -- the tiled KITTI
   protocols (evaluate_mf.py:985-1053 / :919-982): fixed-height bottom padding, overlapping crops of the training size, crops
   blended with a Gaussian weight each (streamflow_amd.tiling, the sf_tile_blend kernel); same scoring.
+* ``validate_spring_mf(model, iters, root, tqdm_miniters, nframes, split)`` / ``spring_report`` -- evaluate_mf.py:50-102 over the
+  Spring layout ``root/train/<scene>/frame_{left,right}/*.png`` + ``flow_{FW,BW}_<cam>/*.flo5`` (forward and backward clips, the
+  ground truth subsampled [::2, ::2]); device flows are scored where they are by the sf_flow_score kernel (ops.flow_score),
+  host flows by streamflow_amd.scoring.score_host with the same arithmetic.
 
 ``model`` is anything with the reference's test-mode call ``model(images: list of [1,3,H,W] in 0..255, iters=.., test_mode=True)
 -> list of nframes - 1 flows [1,2,H,W]`` (streamflow_amd.SKFlow_MF8, or the CPU oracle wrapped the same way in the tests).
-Files are read with this package's own codecs (flow_io.py: PNG, .flo, KITTI 16-bit PNG).  Host-side plumbing: the only kernel
-launched here is the tile blend of the tiled validators (ops.tile_blend) for models without ``forward_tiled``.
+Files are read with this package's own codecs (flow_io.py: PNG, .flo, KITTI 16-bit PNG; flo5.py: Spring's .flo5).  Host-side
+plumbing: the kernels launched here are the tile blend of the tiled validators (ops.tile_blend) for models without
+``forward_tiled`` and the Spring scoring (ops.flow_score).
 """
 from __future__ import annotations
 
@@ -138,6 +143,82 @@ def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str]
     f1 = float(100 * np.mean(np.concatenate(out_list)))
     print("Validation KITTI: %f, %f" % (epe, f1))
     return {"kitti_epe": epe, "kitti_f1": f1}
+
+
+# ---- Spring (evaluate_mf.py:50-102, core/mf_datasets.py:99-213) ---------------------------------------------------------------
+def _spring_gt_path(scene_dir: str, direction: str, cam: str, n: int, index: int) -> str:
+    """Ground-truth file of pair `index` of the (forward or reversed) frame list: forward flow_FW_<cam>_{index + 1:04d},
+    backward flow_BW_<cam>_{n - index:04d} (mf_datasets.py:126-127, :148-149)."""
+    number = index + 1 if direction == "FW" else n - index
+    return os.path.join(scene_dir, f"flow_{direction}_{cam}", f"flow_{direction}_{cam}_{number:04d}.flo5")
+
+
+@torch.no_grad()
+def spring_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", nframes: int = 3, device: Optional[torch.device] = None,
+                  scenes: Optional[Sequence[str]] = ("0041",)) -> Dict[str, float]:
+    """The Spring validation of the reference (validate_spring_mf over SpringEval) as a dictionary: 'epe', '1px', '3px', '5px',
+    'spring_1px', 'spring_1px_s0_10', 'spring_1px_s10_40', 'spring_1px_s40' (what the reference prints), plus 'epe_valid',
+    'pixels', 'valid_pixels' and 'pairs'.
+
+    Walks root/train/<scene>/frame_{left,right}/*.png: per scene (sorted), per camera (left, right), the forward clips, then the
+    backward clips (the same frames reversed), both on sintel_clip_schedule; pair k of a clip starting at a is scored against
+    ground-truth file a + k (_spring_gt_path), subsampled [::2, ::2] as the reference does; pairs with frame id -1 are skipped.
+    Flows on the GPU are scored where they are by ops.flow_score into one device accumulator (one copy to the host at the end);
+    host flows (a CPU model) by scoring.score_host, with the same arithmetic (scoring.py states how both relate to the reference).
+    Reference quirks kept: only scene 0041 by default (the hard-coded train / val split, mf_datasets.py:117; scenes=None scores
+    every scene); the dataset's |flow| < 1000 valid maps are not used; 'epe' is NaN as soon as one ground-truth pixel is NaN."""
+    from . import flo5, ops, scoring
+    dev = device or _device_of(model)
+    train = os.path.join(root, "train")
+    names = [s for s in _scenes(train) if scenes is None or s in scenes]
+    acc_host = np.zeros(scoring.LEN, np.float64)
+    acc_dev = {}
+    pairs = 0
+    step = 2                                                            # SpringEval(subsample_groundtruth=True)
+    for scene in names:
+        scene_dir = os.path.join(train, scene)
+        for cam in ("left", "right"):
+            frames = sorted(glob.glob(os.path.join(scene_dir, f"frame_{cam}", "*.png")))
+            n = len(frames)
+            for direction, order in (("FW", frames), ("BW", frames[::-1])):
+                for first, ids in sintel_clip_schedule(n, nframes):
+                    images = [_image(p)[None].to(dev) for p in order[first:first + nframes]]
+                    padder = InputPadder(images[0].shape)
+                    flows = model(padder.pad_list(images), iters=iters, test_mode=True)
+                    for k in range(nframes - 1):
+                        if ids[k] == -1:
+                            continue
+                        gt = flo5.read_flo5(_spring_gt_path(scene_dir, direction, cam, n, first + k))
+                        pred = padder.unpad(flows[k][0])
+                        if pred.is_cuda:
+                            acc = acc_dev.get(pred.device)
+                            if acc is None:
+                                acc = acc_dev[pred.device] = torch.zeros(scoring.LEN, dtype=torch.float64, device=pred.device)
+                            ops.flow_score(pred.float(), torch.from_numpy(np.ascontiguousarray(gt, np.float32)).to(pred.device),
+                                           acc, step)
+                        else:
+                            scoring.score_host(pred.float().numpy(), gt, acc_host, step)
+                        pairs += 1
+    if pairs == 0:
+        raise RuntimeError(f"spring_report: no pairs scored under {train} (scenes={scenes})")
+    for acc in acc_dev.values():
+        acc_host = acc_host + acc.cpu().numpy()
+    rep = scoring.report(acc_host)
+    rep["pairs"] = pairs
+    print("Validation EPE: %f, 1px: %f, 3px: %f, 5px: %f" % (rep["epe"], rep["1px"], rep["3px"], rep["5px"]))
+    print("Spring 1px: %f, 1px(s0~10): %f, 1px(s10~40): %f, 1px(s40+): %f" % (
+        rep["spring_1px"], rep["spring_1px_s0_10"], rep["spring_1px_s10_40"], rep["spring_1px_s40"]))
+    return rep
+
+
+@torch.no_grad()
+def validate_spring_mf(model: Callable, iters: int = 6, root: str = "/data/Sintel", tqdm_miniters: int = 1, nframes: int = 3,
+                       split: bool = False, device: Optional[torch.device] = None, scenes: Optional[Sequence[str]] = ("0041",)) -> float:
+    """The reference's return value: the mean EPE over every scored pixel (evaluate_mf.py:50-102).  `split` and `tqdm_miniters`
+    are accepted and ignored (the reference's SpringEval applies its 0041 split whatever `split` says; there is no progress bar)."""
+    if hasattr(model, "eval"):
+        model.eval()
+    return spring_report(model, iters, root, nframes, device=device, scenes=scenes)["epe"]
 
 
 # ---- tiled inference (evaluate_mf.py:858-1053) ------------------------------------------------------------------------------

@@ -1228,6 +1228,31 @@ def flow_to_image(flows: torch.Tensor, clip_flow: Optional[float] = None, rad_ma
     return (out, ws) if return_rad_max else out
 
 
+@on_tensor_device
+def flow_score(pred: torch.Tensor, gt: torch.Tensor, acc: torch.Tensor, step: int = 1) -> None:
+    """Add the Spring scores of one field to `acc` (sf_flow_score; reference evaluate_mf.py:60-102): pred fp32 [2, h, w] on the GPU,
+    any view whose rows are contiguous (padder.unpad(flow[0]) of the model's padded output needs no copy); gt fp32 [Hg, Wg, 2]
+    contiguous (read_flo5's array), pixel (y, x) scored against gt[step * y, step * x]; acc float64 [scoring.LEN] contiguous on the
+    same device.  Enqueued on the current stream, no synchronisation; streamflow_amd.scoring.report(acc) forms the dictionary."""
+    from . import scoring
+    if not (pred.is_cuda and gt.is_cuda and acc.is_cuda) or len({pred.device, gt.device, acc.device}) != 1:
+        raise RuntimeError(f"flow_score: pred, gt and acc must be on one GPU (got {pred.device}, {gt.device}, {acc.device}); "
+                           "host flows are scored by streamflow_amd.scoring.score_host")
+    if pred.dtype != torch.float32 or pred.dim() != 3 or pred.shape[0] != 2 or pred.stride(2) != 1:
+        raise RuntimeError(f"flow_score: pred must be fp32 [2, h, w] with contiguous rows (got {pred.dtype} {tuple(pred.shape)}, "
+                           f"strides {pred.stride()})")
+    if gt.dtype != torch.float32 or not gt.is_contiguous():
+        raise RuntimeError(f"flow_score: gt must be contiguous fp32 [Hg, Wg, 2] (got {gt.dtype}, contiguous={gt.is_contiguous()})")
+    if acc.dtype != torch.float64 or acc.numel() != scoring.LEN or not acc.is_contiguous():
+        raise RuntimeError(f"flow_score: acc must be a contiguous float64 vector of {scoring.LEN} (got {acc.dtype} {tuple(acc.shape)})")
+    h, w = int(pred.shape[1]), int(pred.shape[2])
+    scoring.check_gt(tuple(gt.shape), h, w, int(step))
+    ws = torch.empty(scoring.WS_BYTES, dtype=torch.uint8, device=pred.device)
+    _lib.check(_lib.load().sf_flow_score(pred.data_ptr(), pred.stride(0), pred.stride(1), gt.data_ptr(), int(gt.shape[0]),
+                                         int(gt.shape[1]), int(step), h, w, acc.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         _lib.stream()), "sf_flow_score")
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None

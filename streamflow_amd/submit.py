@@ -10,6 +10,9 @@
   ``args.multi_root/testing/image_2/000NNN_FF.png``, frames 12 - nframes .. 11, the padder in its default ('sintel') mode as the
   reference has it there, the LAST flow as the 16-bit PNG ``output_path/000NNN_10.png``; the colour image goes to
   ``vis_path/flow/000NNN_10.png`` when `vis_path` is given (the reference always writes ``vis_kitti2/`` into the working directory).
+* ``create_spring_submission_mf(args, model, iters, output_path, nframes)`` -- evaluate_mf.py:25-48 over
+  ``args.spring_root/test/<scene>/frame_{left,right}/*.png``: forward and backward clips of every scene and camera, each flow as
+  ``output_path/<scene>/flow_<FW|BW>_<cam>/flow_<FW|BW>_<cam>_%04d.flo5`` (flo5.write_flo5, gzip level 5); no colour images.
 
 ``model`` is the reference's test-mode call (see evaluate.py).  The colour images of one clip are made on the device by ONE
 ``ops.flow_to_image`` call before the flows are copied to the host; ``vis=False`` launches no kernel, which lets the writers run
@@ -98,6 +101,39 @@ def create_sintel_submission_mf_warmup(args, model: Callable, iters: int, output
 
             for (_, ids), flows in zip(schedule, predict_clips_warm_start(model, clips(), iters=iters)):
                 _write_sintel_clip([padder.unpad(f[0]) for f in flows], ids, output_path, dstype, scene, vis)
+
+
+@torch.no_grad()
+def create_spring_submission_mf(args, model: Callable, iters: int, output_path: str = "sintel_submission", nframes: int = 4,
+                                device: Optional[torch.device] = None) -> None:
+    """Create the submission tree for the Spring leaderboard (evaluate_mf.py:25-48 over SpringSubmission, mf_datasets.py:47-97):
+    every scene of ``args.spring_root/test`` (sorted), both cameras, the forward clips and then the backward clips (the frames
+    reversed), every clip from a cold start on sintel_clip_schedule.  Each pair whose frame id is not -1 is written with
+    flo5.write_flo5 (gzip level 5, the reference's) as ``output_path/<scene>/flow_<FW|BW>_<cam>/flow_<FW|BW>_<cam>_%04d.flo5`` with
+    the 1-based id j + 1 forward and n - j backward (j: the source frame's index in the forward or reversed list).  As in the
+    reference there are no colour images, and the default output_path is the reference's 'sintel_submission'."""
+    from . import flo5
+    _eval_mode(model)
+    dev = device or _device_of(model)
+    test_root = os.path.join(args.spring_root, "test")
+    for scene in _scenes(test_root):
+        for cam in ("left", "right"):
+            frames = sorted(glob.glob(os.path.join(test_root, scene, f"frame_{cam}", "*.png")))
+            n = len(frames)
+            for direction, order in (("FW", frames), ("BW", frames[::-1])):
+                output_dir = os.path.join(output_path, scene, f"flow_{direction}_{cam}")
+                os.makedirs(output_dir, exist_ok=True)
+                for first, ids in sintel_clip_schedule(n, nframes):
+                    images = [_image(p)[None].to(dev) for p in order[first:first + nframes]]
+                    padder = InputPadder(images[0].shape)
+                    flows = model(padder.pad_list(images), iters=iters, test_mode=True)
+                    assert len(flows) == len(ids) - 1
+                    for k, j in enumerate(ids[:-1]):
+                        if j == -1:
+                            continue
+                        number = j + 1 if direction == "FW" else n - j
+                        flo5.write_flo5(os.path.join(output_dir, f"flow_{direction}_{cam}_%04d.flo5" % number),
+                                        padder.unpad(flows[k][0]).permute(1, 2, 0).float().cpu().numpy(), compression_level=5)
 
 
 @torch.no_grad()
