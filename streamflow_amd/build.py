@@ -23,8 +23,8 @@ LIB = os.path.join(HERE, "libstreamflow_hip.so")
 ASAN_OBJ = os.path.join(CSRC, "build_asan")
 ASAN_LIB = os.path.join(HERE, "libstreamflow_hip_asan.so")
 SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip"]
-HEADERS = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "gemm_epilogue.h"), os.path.join(CSRC, "split_operand.h"),
-           os.path.join(HERE, "..", "include", "streamflow_hip.h")]
+HEADERS = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "weight_ring.h"), os.path.join(CSRC, "gemm_epilogue.h"),
+           os.path.join(CSRC, "split_operand.h"), os.path.join(HERE, "..", "include", "streamflow_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function",
          # per-kernel registers / scratch / occupancy as compiler remarks: kept next to every object (<name>.res) and checked

@@ -16,16 +16,13 @@
 //   * layer 2 accumulates ALL M2 output rows of the 16 pixels (M2 / 16 tiles x 4 registers) while the hidden streams past;
 //   * both layers' weights stream through LDS in ONE linear sequence of 1-KB fragments, packed on the host in the order the
 //     MFMAs consume them (per 32 hidden rows: 2 NK1 PM1 fragments of W1, then NT2 PM2 of W2', padded to whole 16-KB stages):
-//     the DMA addressing is "next 16 KB", two stages ping-pong, one barrier per stage.
+//     the DMA addressing is "next 16 KB", a ring of three stages, one barrier per stage (csrc/weight_ring.h).
 // PM1 / PM2 = MFMA products per layer (1: the round-to-nearest fp16 weight, 2: hi + lo); activations enter as fp16, fp32
 // accumulation -- the config-2 arithmetic class (SF_PRECISION_F16X2 / SF_PRECISION_F16 per layer).
 // MODE 0 (an ffn2 pair, update.py:36):  out = y  or gelu(y), as fp16 k-octet planes and / or fp32 planes.
 // MODE 1 (an ffn1 pair, update.py:31-33 first two lines): x1 = gelu(x + y); x2 = gelu(x1 + dw1x1(x1)); out = x2 as fp16 ROWS (the
 //         depthwise K x K kernel's input); the residual x is re-read from the k-octet input (the operand itself).
-#include "sf_common.h"
-
-#include <cstdlib>
-#include <type_traits>
+#include "weight_ring.h"
 
 namespace {
 
@@ -34,33 +31,19 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
 using sf::f32x2;
+using sf::static_for;
+using sf::wait_vm;
 
 constexpr int kPxWave = 16;                                // pixels per wave; a workgroup = NW waves = 16 NW pixels (NW = 4 or 8)
 constexpr int S = 16;                                      // fragments per stage
 constexpr int kStage = S * 1024;
-#ifndef SF_PAIR_RING
-#define SF_PAIR_RING 3                                     // stages in flight + 1: the ring of the weight stream (A/B knob)
-#endif
-constexpr int RING = SF_PAIR_RING;
-#ifndef SF_PAIR_ONE_LOADER
-#define SF_PAIR_ONE_LOADER 0
-#endif
+constexpr int RING = 3;                                    // stages in flight + 1: the ring of the weight stream
 
 constexpr int kOob = 1 << 30;                              // byte offset beyond every buffer range (host-checked spans < 2^30)
 constexpr int kMaxH = 608, kMaxM2 = 384;                   // hidden rows whose bias is kept in LDS; output rows (24 tiles)
 
-#ifdef SF_PAIR_TIMERS
-#define SF_PT_STAMP(acc_) { const long long t_ = __builtin_readcyclecounter(); acc_ += t_ - tprev; tprev = t_; }
-#else
-#define SF_PT_STAMP(acc_)
-#endif
-
 struct PairArgs {
-#ifdef SF_PAIR_TIMERS
-    long long* ts;        // SF_PAIR_TS_BUF: per-wave phase cycle sums (tools/ffn_pair_timers.py; -DSF_PAIR_TIMERS builds only)
-#endif
     SfFfnPair p;
     int ntile;            // pixel tiles per image
     int hp;               // hidden row pairs of 16 = ceil(H / 32)
@@ -69,25 +52,11 @@ struct PairArgs {
     int64_t w_bytes;      // bytes of the packed weight stream
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 template <int NK1, int NT2, int PM1, int PM2, int MODE, int NW>
 __global__ __launch_bounds__(NW * 64, (NW == 8) ? 4 : ((NK1 > 8 && MODE >= 1) ? 2 : 3)) void ffn_pair_kernel(const PairArgs a) {
     const SfFfnPair& g = a.p;
     constexpr int kWaves = NW, kThreads = NW * 64, kPxWg = NW * kPxWave;
     constexpr int NA = 2 * NK1 * PM1, NB = NT2 * PM2, F = NA + NB, NSTG = (F + S - 1) / S;
-    constexpr int PCS = S / kWaves;                               // 1-KB pieces a wave moves per stage
     // LDS: the weight ring + the layer-1 bias (read at the top of every 32-row step); the other parameters are read from global
     // memory outside the streaming loop (where a plain load cannot disturb the counted waits of the DMA queue)
     __shared__ __attribute__((aligned(1024))) char smem[RING * kStage + (kMaxH + kMaxM2) * 4];
@@ -102,29 +71,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 8) ? 4 : ((NK1 > 8 && MODE >= 1) ? 
     const int px = tile * kPxWg + wave * kPxWave + l15;
     const bool pin = px < g.N;
 
-    // ---- the weight stream: stage s = bytes [s * 16 KB, (s + 1) * 16 KB) of the packed buffer; wave w moves pieces w, w + 4, ... ----
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.wstream), 0, (int)a.w_bytes, 0x00020000);
-    // (stages requested past the end of the stream -- the loop keeps the request count per trip constant -- re-read the LAST stage
-    // into a slot nobody reads any more: the stage offset travels in the scalar offset, which the raw-buffer range check of gfx9
-    // does not cover, so "out of range: zeros" must not be relied on: ADVICE r5)
-    const int last_stage = (int)(a.w_bytes / kStage) - 1;
-    auto issue_stage = [&](int s, int slot) {
-        const int sc = min(s, last_stage);
-#pragma unroll
-        for (int i = 0; i < S / kWaves; ++i) {
-            const int piece = wave + kWaves * i;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + slot * kStage + piece * 1024), 16, lane * 16,
-                                                     sc * kStage + piece * 1024, 0, 0);
-        }
-    };
-#ifdef SF_PAIR_TIMERS
-    const long long ts0 = __builtin_readcyclecounter();
-    long long t_issue = 0, t_mma = 0, t_drain = 0, t_bar = 0, tprev = ts0;
-#endif
+    // ---- the weight stream: a.hp * NSTG stages of 16 KB ----
+    sf::WeightRing<S, RING, kWaves> ring(g.wstream, a.w_bytes, smem, wave, lane);
+    // the ring's prologue, guarded (a stream may be ONE stage long).  Written out here on purpose, not as a guard inside
+    // ring.prologue(): inside a member function hipcc nests the two tests and every instantiation of this kernel gets other
+    // scalar control flow than it had with its own ring (profiles/weight_ring_refactor.md, section 1)
     const int nstage = a.hp * NSTG;
 #pragma unroll
     for (int i = 0; i < RING - 1; ++i)
-        if (i < nstage) issue_stage(i, i);
+        if (i < nstage) ring.issue(i, i);
 
     // ---- epilogue parameters ----
     for (int i = tid; i < a.hp * 32; i += kThreads) sb1[i] = (i < g.H && g.bias1) ? g.bias1[i] : 0.f;
@@ -153,11 +108,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8) ? 4 : ((NK1 > 8 && MODE >= 1) ? 
 #pragma unroll
     for (int t = 0; t < NT2; ++t) acc2[t] = *reinterpret_cast<const f32x4*>(sb2 + 16 * t + 4 * kq);
 
-#ifdef SF_PAIR_TIMERS
-    const long long ts1 = __builtin_readcyclecounter();
-    tprev = ts1;
-#endif
-    int gs = 0, slot = 0;                                         // global stage index, its ring slot
     for (int m = 0; m < a.hp; ++m) {
         f32x4 a1[2];
         a1[0] = *reinterpret_cast<const f32x4*>(sb1 + 32 * m + 4 * kq);
@@ -165,21 +115,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8) ? 4 : ((NK1 > 8 && MODE >= 1) ? 
         f16x8 hf = {};
         static_for<0, NSTG>([&](auto st_tag) {
             constexpr int st = decltype(st_tag)::value;
-            // stage gs + RING - 1 goes into the slot every wave finished reading before the barrier that ended the previous stage
-            // (issued past the end too -- clamped to the last stage -- so that the counted wait below sees the same queue every trip)
-#if SF_PAIR_ONE_LOADER
-            // (experiment: ONE wave per stage issues all its pieces -- fewer waves queueing on the CU's address path at a time)
-            if (wave == gs % kWaves) {
-#pragma unroll
-                for (int i = 0; i < S; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + (slot == 0 ? RING - 1 : slot - 1) * kStage + i * 1024), 16,
-                                                             lane * 16, min(gs + RING - 1, last_stage) * kStage + i * 1024, 0, 0);
-            }
-#else
-            issue_stage(gs + RING - 1, slot == 0 ? RING - 1 : slot - 1);
-#endif
-            SF_PT_STAMP(t_issue)
-            const char* sp = smem + slot * kStage + lane * 16;
+            const char* sp = ring.begin();
             static_for<0, S>([&](auto i_tag) {
                 constexpr int i = decltype(i_tag)::value, f = st * S + i;
                 if constexpr (f == NA) {
@@ -203,32 +139,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 8) ? 4 : ((NK1 > 8 && MODE >= 1) ? 
                     acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(sp + i * 1024), hf, acc2[t], 0, 0, 0);
                 }
             });
-            // Every fragment read of this stage must have EXECUTED before the barrier: the slot is refilled by whichever wave passes
-            // the barrier first, and a read that was only issued (hipcc sinks the last MFMAs and their lgkmcnt waits below the
-            // s_barrier -- the builtin is no memory barrier to it) then races with the refill's DMA.  Seen as run-to-run differences
-            // (tests/test_gpu_ffn_pair.py::test_ffn_pair_is_deterministic) with both ring depths; the explicit drain removed them.
-            SF_PT_STAMP(t_mma)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if SF_PAIR_ONE_LOADER
-            static_assert(!SF_PAIR_ONE_LOADER || RING == 3, "one-loader experiment: ring of 3");
-            if (wave == (gs + kWaves - 1) % kWaves) wait_vm<0>();  // the wave that issued stage gs + 1 (at the top of stage gs - 1)
-#else
-            wait_vm<PCS * (RING - 2)>();                           // this wave's pieces of the NEXT stage have landed (later ones fly on) ...
-#endif
-            SF_PT_STAMP(t_drain)
-            __builtin_amdgcn_s_barrier();                          // ... everyone's; nobody reads this stage's slot any more
-            SF_PT_STAMP(t_bar)
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            ++gs;
-            slot = (slot == RING - 1) ? 0 : slot + 1;
+            ring.end();
         });
     }
 
-#ifdef SF_PAIR_TIMERS
-    const long long ts2 = __builtin_readcyclecounter();
-#endif
-    wait_vm<0>();                                                  // (pieces requested past the end must land before the LDS is released)
+    ring.drain();
     constexpr bool kR32 = MODE == 2;                               // MODE 2 = mode 1 with the residual from fp32 planes (SfFfnPair.R32)
     if constexpr (MODE >= 1) {                                     // the depthwise 1x1 parameters into the (now idle) ring
         __syncthreads();
@@ -353,14 +268,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8) ? 4 : ((NK1 > 8 && MODE >= 1) ? 
         }
         }
     }
-#ifdef SF_PAIR_TIMERS
-    if (a.ts && lane == 0 && blockIdx.x < 8192) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        long long* d = a.ts + ((int64_t)blockIdx.x * NW + wave) * 8;
-        d[0] = ts1 - ts0; d[1] = t_issue; d[2] = t_mma; d[3] = t_drain; d[4] = t_bar; d[5] = ts2 - ts1; d[6] = __builtin_readcyclecounter() - ts2;
-        d[7] = nstage;
-    }
-#endif
 }
 
 template <int NK1, int NT2, int MODE, int NW>
@@ -415,9 +322,6 @@ extern "C" int sf_ffn_pair(const SfFfnPair* p, void* stream) {
         SF_REQUIRE(g.ldc16 >= g.N && ((int64_t)(g.M2 - 1) * g.ldc16 + g.N) * 2 < lim, "sf_ffn_pair: C16 rows: ldc16 >= N, image < 1 GiB");
     }
     PairArgs a;
-#ifdef SF_PAIR_TIMERS
-    a.ts = getenv("SF_PAIR_TS_BUF") ? (long long*)strtoull(getenv("SF_PAIR_TS_BUF"), nullptr, 0) : nullptr;
-#endif
     a.p = g;
     a.ntile = 0;
     a.hp = (g.H + 31) / 32;

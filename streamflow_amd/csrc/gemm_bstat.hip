@@ -18,8 +18,7 @@
 // per fragment, converted / packed once) -- it is read exactly once per pixel tile, so its format hardly matters any more.
 // Epilogues as sf_gemm's (bias, GELU, residual, depthwise 1 x 1, AXPY), straight from the accumulator layout: a lane holds 4
 // consecutive rows of one pixel = 8 bytes of a k-octet, or four dwords of four 128-byte row segments.
-#include "sf_common.h"
-#include <type_traits>
+#include "weight_ring.h"
 #include <cstdlib>
 
 namespace {
@@ -33,6 +32,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void* lds_ptr;
 using sf::f32x2;
+using sf::gelu_poly_n;
+using sf::static_for;
+using sf::wait_vm;
 
 constexpr int kThreads = 256;          // 4 waves x 32 pixels
 constexpr int BN = 128;
@@ -83,10 +85,6 @@ __device__ __forceinline__ WorkItem work_item(const BsArgs& a) {
     return wi;
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {                 // s_waitcnt vmcnt(N) only (expcnt / lgkmcnt untouched)
-    __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-}
 // vmcnt(P + e) for the wave-uniform epilogue size e: the first two stages of an m-step have the previous epilogue's stores
 // (and the next residual loads) BEHIND the weight pieces they wait for; a smaller count would wait for those stores too
 template <int P>
@@ -105,33 +103,7 @@ __device__ __forceinline__ void wait_vm_epi(int e) {
     }
 }
 
-// GELU of NP pairs at a time with the Horner chains INTERLEAVED (coefficient loop outside, pair loop inside).  Evaluated
-// pair by pair the epilogue is bound by the latency of one dependent chain -- 14 packed instructions at ~11 cycles each, 160
-// cycles per pair measured with the phase timers, 2550 of an m-step's 3670 epilogue cycles -- because hipcc keeps the pairs
-// apart to save registers; four chains in flight hide each other's latency.  Same operations per value as sf::gelu_poly2 /
-// sf::gelu_erf2 (bit-identical results).
-template <int NP>
-__device__ __forceinline__ void gelu_poly_n(f32x2 (&x)[NP]) {
-    f32x2 xc[NP], t[NP], p[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        xc[i][0] = __builtin_amdgcn_fmed3f(x[i][0], -4.2426405f, 4.2426405f);
-        xc[i][1] = __builtin_amdgcn_fmed3f(x[i][1], -4.2426405f, 4.2426405f);
-        t[i] = xc[i] * xc[i];
-        p[i] = sf::splat2(1.12535e-10f);
-    }
-    constexpr float c[8] = {-1.074371e-08f, 4.5365834e-07f, -1.12924145e-05f, 0.0001871811f, -0.0022188f, 0.019636236f,
-                            -0.13269384f, 0.79780626f};
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int i = 0; i < NP; ++i) p[i] = __builtin_elementwise_fma(p[i], t[i], sf::splat2(c[k]));
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const f32x2 h = sf::splat2(0.5f) * __builtin_elementwise_max(x[i], sf::splat2(-4.2426405f));
-        x[i] = __builtin_elementwise_fma(h, xc[i] * p[i], h);
-    }
-}
+// sf::gelu_poly_n's counterpart for the erf form: same operations per value as sf::gelu_erf2 (bit-identical results)
 template <int NP>
 __device__ __forceinline__ void gelu_erf_n(f32x2 (&x)[NP]) {
     f32x2 z[NP], z2[NP], p[NP], q[NP];
@@ -584,14 +556,6 @@ __global__ __launch_bounds__(kThreads, (PM == 1 && NKS <= 16 && RES == 0) ? 4 : 
 // groups that are scheduled BETWEEN the MFMAs of tile i + 1 (sched_group_barrier: one MFMA, one fragment read, a few VALU).
 // The weight stream is fragment-granular: one 1-KB DMA piece = the (32 rows x 16 k) A fragment of one MFMA, laid down in LDS
 // in the order the MFMAs consume it, in stages of S fragments (S divides the fragments of a tile: no stage straddles a tile).
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 template <int NF> struct StageF { static constexpr int value = (NF % 16 == 0) ? 16 : (NF % 20 == 0) ? 20 : (NF % 12 == 0) ? 12 : 8; };
 
 template <int NKS, int PM>

@@ -7,13 +7,10 @@
 // 64 k + s (k = neighbour, s = 8 i + j the sub-pixel) lives in tile 4 k + s / 16 at (kq, register) = ((s % 16) / 4, s % 4), i.e.
 // the same lane and register for every k.  So: a wave owns 16 pixels, accumulates all 36 row tiles (144 registers), and its epilogue
 // is the softmax + combination + the 16-byte stores of four horizontally adjacent sub-pixels per lane (a wave's 16 pixels of a row
-// make 512-byte runs).  Weights stream as in csrc/ffn_pair.hip (one fragment stream through a 3-stage LDS ring).
+// make 512-byte runs).  Weights stream through the shared 3-stage LDS ring (csrc/weight_ring.h).
 // Input: the k-octet fp16 copy of relu(mask.0(net)) (sf_gemm's c_f16 = 3 output); arithmetic: activations fp16, weights fp16 (pm = 1)
 // or hi + lo (pm = 2), fp32 accumulation and softmax.
-#include "sf_common.h"
-
-#include <cstdlib>
-#include <type_traits>
+#include "weight_ring.h"
 
 namespace {
 
@@ -21,11 +18,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
+using sf::static_for;
+using sf::wait_vm;
 
 constexpr int kK = 256, kM = 576, kTiles = kM / 16, kKs = kK / 32;
 constexpr int kWaves = 4, kThreads = 256, kPxWave = 16, kPxWg = kWaves * kPxWave;
-constexpr int S = 16, kStage = S * 1024, RING = 3, PCS = S / kWaves;
+constexpr int S = 16, kStage = S * 1024, RING = 3;
 constexpr int kOob = 1 << 30;
 
 struct MuArgs {
@@ -33,19 +31,6 @@ struct MuArgs {
     int ntile;
     int64_t w_bytes;
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 template <int PM>
 __global__ __launch_bounds__(kThreads, 2) void mask_upsample_kernel(const MuArgs a) {
@@ -63,22 +48,8 @@ __global__ __launch_bounds__(kThreads, 2) void mask_upsample_kernel(const MuArgs
     const int px = tile * kPxWg + wave * kPxWave + l15;
     const bool pin = px < P;
 
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.wstream), 0, (int)a.w_bytes, 0x00020000);
-    // (stages requested past the end of the stream -- the loop keeps the request count per trip constant -- re-read the LAST stage
-    // into a slot nobody reads any more: the stage offset travels in the scalar offset, which the raw-buffer range check of gfx9
-    // does not cover, so "out of range: zeros" must not be relied on: ADVICE r5)
-    const int last_stage = (int)(a.w_bytes / kStage) - 1;
-    auto issue_stage = [&](int s, int slot) {
-        const int sc = min(s, last_stage);
-#pragma unroll
-        for (int i = 0; i < PCS; ++i) {
-            const int piece = wave + kWaves * i;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + slot * kStage + piece * 1024), 16, lane * 16,
-                                                     sc * kStage + piece * 1024, 0, 0);
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < RING - 1; ++i) issue_stage(i, i);
+    sf::WeightRing<S, RING, kWaves> ring(g.wstream, a.w_bytes, smem, wave, lane);
+    ring.prologue();
     for (int i = tid; i < kM; i += kThreads) sbias[i] = g.bias ? g.bias[i] : 0.f;
 
     // ---- operand: the 256 channels of this lane's pixel (k-octet 4 s + kq of k-step s) ----
@@ -108,21 +79,15 @@ __global__ __launch_bounds__(kThreads, 2) void mask_upsample_kernel(const MuArgs
     for (int t = 0; t < kTiles; ++t) acc[t] = *reinterpret_cast<const f32x4*>(sbias + 16 * t + 4 * kq);
 
     static_for<0, kTiles / TPS>([&](auto j_tag) {
-        constexpr int j = decltype(j_tag)::value, slot = j % RING;
-        issue_stage(j + RING - 1, (slot + RING - 1) % RING);      // (past the end: the last stage again)
-        const char* sp = smem + slot * kStage + lane * 16;
+        constexpr int j = decltype(j_tag)::value;
+        const char* sp = ring.begin();
         static_for<0, S>([&](auto i_tag) {
             constexpr int i = decltype(i_tag)::value, t = j * TPS + i / FT, ks = (i % FT) / PM;
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(sp + i * 1024), b[ks], acc[t], 0, 0, 0);
         });
-        // every fragment read of the stage has EXECUTED before the barrier (ffn_pair.hip: the refill race)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        wait_vm<PCS * (RING - 2)>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        ring.end();
     });
-    wait_vm<0>();
+    ring.drain();
 
     // ---- softmax over the nine neighbours per sub-pixel, convex combination, 16-byte stores ----
     // sub-pixel s = 16 gq + 4 kq + e  ->  (i, j) = (s >> 3, s & 7) = (2 gq + (kq >> 1), 4 (kq & 1) + e): out[c][8 y + i][8 x + j]

@@ -13,10 +13,9 @@
 //   * the 1.5 C hidden of ffn2 32 rows at a time (one accumulator tile), turned into two B fragments the same way and consumed at
 //     once by ffn2.2's accumulators (M2 / 32 tiles, resident for the whole kernel).
 // All three layers' weights are ONE host-packed stream of 1-KB MFMA fragments in consumption order (units padded to 16-fragment
-// stages), pulled L2 -> LDS through the 3-stage ring of csrc/ffn_pair.hip, one barrier per stage, shared by the 4 waves (128 pixels).
+// stages), pulled L2 -> LDS through the 3-stage ring of csrc/weight_ring.h, one barrier per stage, shared by the 4 waves (128 pixels).
 // The rounding points are those of the three launches (x4 and the hidden leave as fp16; accumulation fp32; weights hi + lo or hi).
-#include "sf_common.h"
-#include <type_traits>
+#include "weight_ring.h"
 
 namespace {
 
@@ -26,18 +25,16 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
 using sf::f32x2;
+using sf::gelu_poly_n;
+using sf::static_for;
+using sf::wait_vm;
 
 constexpr int kThreads = 256, kWaves = 4;
 constexpr int BN = 128;                      // pixels per workgroup (4 waves x 32)
-#ifndef SF_TAIL_V2
-#define SF_TAIL_V2 0      // 1: 32-fragment stages in a ring of TWO (half the barriers), pw as one unit, G hidden tiles per unit (A/B)
-#endif
-constexpr int S = SF_TAIL_V2 ? 32 : 16;      // fragments per stage
+constexpr int S = 16;                        // fragments per stage
 constexpr int kStage = S * 1024;
-constexpr int RING = SF_TAIL_V2 ? 2 : 3;
-constexpr int PCS = S / kWaves;              // DMA pieces per wave and stage
+constexpr int RING = 3;
 constexpr int kOob = 1 << 30;
 constexpr int kMaxC = 384, kMaxH = 576, kMaxM = 192;
 
@@ -48,41 +45,6 @@ struct TailArgs {
     int64_t w_bytes;      // bytes of the packed weight stream
     int x_span;           // bytes of one image of X the kernel may address
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14)); }
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// polynomial GELU of NP pairs with the Horner chains interleaved (csrc/gemm_bstat.hip: same operations per value as sf::gelu_poly2)
-template <int NP>
-__device__ __forceinline__ void gelu_poly_n(f32x2 (&x)[NP]) {
-    f32x2 xc[NP], t[NP], p[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        xc[i][0] = __builtin_amdgcn_fmed3f(x[i][0], -4.2426405f, 4.2426405f);
-        xc[i][1] = __builtin_amdgcn_fmed3f(x[i][1], -4.2426405f, 4.2426405f);
-        t[i] = xc[i] * xc[i];
-        p[i] = sf::splat2(1.12535e-10f);
-    }
-    constexpr float c[8] = {-1.074371e-08f, 4.5365834e-07f, -1.12924145e-05f, 0.0001871811f, -0.0022188f, 0.019636236f,
-                            -0.13269384f, 0.79780626f};
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int i = 0; i < NP; ++i) p[i] = __builtin_elementwise_fma(p[i], t[i], sf::splat2(c[k]));
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const f32x2 h = sf::splat2(0.5f) * __builtin_elementwise_max(x[i], sf::splat2(-4.2426405f));
-        x[i] = __builtin_elementwise_fma(h, xc[i] * p[i], h);
-    }
-}
 
 // gelu(alpha * acc) of a 32-row tile -> the two B fragments (k-steps 0, 1 of the tile) of the next layer.  NP pairs of values per
 // GELU pass (4: four interleaved Horner chains; 2: half the temporaries -- the C >= 256 shapes have no registers to spare)
@@ -110,15 +72,6 @@ __device__ __forceinline__ void tile_to_frags(const f32x16& acc, float alpha, f1
     }
 }
 
-// hidden tiles per phase-2 unit (v2; 1 in v1): G * (2 NC + 2 NM) PM fragments should fill whole 32-fragment stages, G must divide NH
-// (12 at H = 384, 18 at 576, 6 at 192: host-checked)
-constexpr int tail_group(int NC, int NM, int PM) {
-    if (!SF_TAIL_V2) return 1;
-    if (NC == 8 && NM == 6) return PM == 2 ? 4 : 4;             // TF = 56 / 28: 224 / 112 -> 7 / 3.5 stages
-    if (NC == 8 && NM == 4) return PM == 2 ? 2 : 4;             // TF = 48 / 24: 96 / 96
-    return 2;                                                   // (12, 1): 104 / 52; (4, 2): 48 / 24
-}
-
 // NC = C / 32 (tiles of x4 = k-step pairs of pw and ffn2.0), NM = ceil(M2 / 32), PM = MFMA products per weight (2: lo + hi, 1: hi)
 template <int NC, int NM, int PM>
 __global__ __launch_bounds__(kThreads, NC >= 12 ? 1 : 2) void sk_tail_kernel(const TailArgs a) {
@@ -128,11 +81,8 @@ __global__ __launch_bounds__(kThreads, NC >= 12 ? 1 : 2) void sk_tail_kernel(con
     constexpr int NA1 = KS * PM;                                 // fragments of one pw tile
     constexpr int NA2 = KS * PM, NB2 = 2 * NM * PM;              // one hidden tile: ffn2.0's fragments, then ffn2.2's two k-steps
     constexpr int TF = NA2 + NB2;
-    // v1: every pw tile and every hidden tile is a unit of its own, padded to whole stages.  v2: pw is ONE unit (NC tiles), the hidden
-    // tiles come G to a unit (tail_group(): chosen so that G * TF fills whole 32-fragment stages where NH allows)
-    constexpr int G = tail_group(NC, NM, PM);
-    constexpr int U1 = SF_TAIL_V2 ? (NC * NA1 + S - 1) / S : (NA1 + S - 1) / S;
-    constexpr int U2 = (G * TF + S - 1) / S;
+    // every pw tile and every hidden tile is a unit of its own, padded to whole stages
+    constexpr int U1 = (NA1 + S - 1) / S, U2 = (TF + S - 1) / S;
     __shared__ __attribute__((aligned(1024))) char smem[RING * kStage + (kMaxC + kMaxH + kMaxM) * 4];
     float* sb1 = reinterpret_cast<float*>(smem + RING * kStage);
     float* sb2 = sb1 + kMaxC;
@@ -143,21 +93,9 @@ __global__ __launch_bounds__(kThreads, NC >= 12 ? 1 : 2) void sk_tail_kernel(con
     const int tile = blockIdx.x % a.ntile, z = blockIdx.x / a.ntile;
     const int n = tile * BN + wave * 32 + l31, nc = min(n, g.N - 1);
 
-    // ---- the weight stream: stage s = bytes [16 KB s, 16 KB (s + 1)); wave w moves pieces w, w + 4, ...; requests past the end
-    // re-read the last stage (the stage offset travels in the scalar offset, which the raw-buffer range check does not cover) ----
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.wstream), 0, (int)a.w_bytes, 0x00020000);
-    const int last_stage = (int)(a.w_bytes / kStage) - 1;
-    auto issue_stage = [&](int s, int slot) {
-        const int sc = min(s, last_stage);
-#pragma unroll
-        for (int i = 0; i < PCS; ++i) {
-            const int piece = wave + kWaves * i;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + slot * kStage + piece * 1024), 16, lane * 16,
-                                                     sc * kStage + piece * 1024, 0, 0);
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < RING - 1; ++i) issue_stage(i, i);
+    // ---- the weight stream: stages of 16 KB through the shared ring ----
+    sf::WeightRing<S, RING, kWaves> ring(g.wstream, a.w_bytes, smem, wave, lane);
+    ring.prologue();
 
     for (int i = tid; i < NC * 32; i += kThreads) sb1[i] = (i < g.C && g.bias1) ? g.bias1[i] : 0.f;
     for (int i = tid; i < a.nh * 32; i += kThreads) sb2[i] = (i < g.H && g.bias2) ? g.bias2[i] : 0.f;
@@ -184,17 +122,13 @@ __global__ __launch_bounds__(kThreads, NC >= 12 ? 1 : 2) void sk_tail_kernel(con
     wait_vm<0>();
     __syncthreads();
 
-    int gs = 0, slot = 0;                                         // global stage index, its ring slot
     // U stages of the stream: body(fragment index in the unit, LDS address of this lane's 16 bytes of the fragment).  NF = fragments of
-    // the unit that feed an MFMA (the rest is padding); a GELU block runs in front of fragments GP0, GP0 + GPS, ... (GPS = 0: none) and a
-    // tile's accumulator start values (four LDS reads) are fetched in front of fragments TS, 2 TS, ... (TS = 0: none)
-    auto run_unit = [&](auto u_tag, auto nf_tag, auto gp0_tag, auto gps_tag, auto ts_tag, auto&& body) {
-        constexpr int U = decltype(u_tag)::value, NF = decltype(nf_tag)::value, GP0 = decltype(gp0_tag)::value,
-                      GPS = decltype(gps_tag)::value, TS = decltype(ts_tag)::value;
+    // the unit that feed an MFMA (the rest is padding); a GELU block runs in front of fragment GP (GP = 0: none)
+    auto run_unit = [&](auto u_tag, auto nf_tag, auto gp_tag, auto&& body) {
+        constexpr int U = decltype(u_tag)::value, NF = decltype(nf_tag)::value, GP = decltype(gp_tag)::value;
         static_for<0, U>([&](auto st_tag) {
             constexpr int st = decltype(st_tag)::value;
-            issue_stage(gs + RING - 1, (RING == 2) ? (slot ^ 1) : (slot == 0 ? RING - 1 : slot - 1));
-            const char* sp = smem + slot * kStage + lane * 16;
+            const char* sp = ring.begin();
             static_for<0, S>([&](auto i_tag) {
                 constexpr int i = decltype(i_tag)::value;
                 body(std::integral_constant<int, st * S + i>{}, sp + i * 1024);
@@ -209,20 +143,12 @@ __global__ __launch_bounds__(kThreads, NC >= 12 ? 1 : 2) void sk_tail_kernel(con
 #pragma unroll
                 for (int i = 0; i < nm; ++i) {
                     const int f = st * S + i;
-                    if (GPS > 0 && f >= GP0 && (f - GP0) % GPS == 0) __builtin_amdgcn_sched_group_barrier(0x002, 200, 0);   // a GELU block
-                    if (TS > 0 && f > 0 && f % TS == 0) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);               // the next tile's bias
+                    if (GP > 0 && f == GP) __builtin_amdgcn_sched_group_barrier(0x002, 200, 0);   // a GELU block
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     if (i + kAhead < nm) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
             }
-            // every fragment read of the stage has EXECUTED before the barrier (the refill race of csrc/ffn_pair.hip)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            wait_vm<PCS * (RING - 2)>();                           // this wave's pieces of the NEXT stage have landed ...
-            __builtin_amdgcn_s_barrier();                          // ... everyone's; nobody reads this stage's slot any more
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            ++gs;
-            slot = (slot == RING - 1) ? 0 : slot + 1;
+            ring.end();
         });
     };
     auto bias_tile = [&](const float* sb, int t32) {              // accumulator start values of rows 32 t32 ..: the pre-scaled bias
@@ -239,60 +165,38 @@ __global__ __launch_bounds__(kThreads, NC >= 12 ? 1 : 2) void sk_tail_kernel(con
     // ---- phase 1: x4 = gelu((pw + I) x3), tile by tile, as the B fragments of ffn2.0 ----
     using std::integral_constant;
     f16x8 x4[KS];
-#if SF_TAIL_V2
-    {
-        f32x16 acc = bias_tile(sb1, 0);
-        run_unit(integral_constant<int, U1>{}, integral_constant<int, NC * NA1>{}, integral_constant<int, NA1>{}, integral_constant<int, NA1>{},
-                 integral_constant<int, NA1>{}, [&](auto f_tag, const char* p) {
-            constexpr int f = decltype(f_tag)::value;
-            if constexpr (f < NC * NA1) {
-                if constexpr (f > 0 && f % NA1 == 0) {              // the previous tile is complete: its fragments, the next tile's start
-                    tile_to_frags<GNP>(acc, g.alpha1, x4[2 * (f / NA1 - 1)], x4[2 * (f / NA1 - 1) + 1]);
-                    acc = bias_tile(sb1, f / NA1);
-                }
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(p), x[(f % NA1) / PM], acc, 0, 0, 0);
-            }
-        });
-        tile_to_frags<GNP>(acc, g.alpha1, x4[2 * (NC - 1)], x4[2 * (NC - 1) + 1]);
-    }
-#else
     static_for<0, NC>([&](auto t_tag) {
         constexpr int t = decltype(t_tag)::value;
         f32x16 acc = bias_tile(sb1, t);
-        run_unit(integral_constant<int, U1>{}, integral_constant<int, NA1>{}, integral_constant<int, 0>{}, integral_constant<int, 0>{},
-                 integral_constant<int, 0>{}, [&](auto f_tag, const char* p) {
+        run_unit(integral_constant<int, U1>{}, integral_constant<int, NA1>{}, integral_constant<int, 0>{}, [&](auto f_tag, const char* p) {
             constexpr int f = decltype(f_tag)::value;
             if constexpr (f < NA1)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(p), x[f / PM], acc, 0, 0, 0);
         });
         tile_to_frags<GNP>(acc, g.alpha1, x4[2 * t], x4[2 * t + 1]);
     });
-#endif
 
-    // ---- phase 2: per 32 hidden rows: ffn2.0 -> gelu -> two k-steps of ffn2.2 (G hidden tiles per unit) ----
+    // ---- phase 2: per 32 hidden rows: ffn2.0 -> gelu -> two k-steps of ffn2.2 ----
     f32x16 acc2[NM];
 #pragma unroll
     for (int m = 0; m < NM; ++m) acc2[m] = bias_tile(sb3, m);
-    for (int th = 0; th < a.nh; th += G) {
+    for (int th = 0; th < a.nh; ++th) {
         f32x16 acch = bias_tile(sb2, th);
         f16x8 hf[2] = {};
-        run_unit(integral_constant<int, U2>{}, integral_constant<int, G * TF>{}, integral_constant<int, NA2>{}, integral_constant<int, TF>{},
-                 integral_constant<int, (G > 1) ? TF : 0>{}, [&](auto f_tag, const char* p) {
+        run_unit(integral_constant<int, U2>{}, integral_constant<int, TF>{}, integral_constant<int, NA2>{}, [&](auto f_tag, const char* p) {
             constexpr int f = decltype(f_tag)::value;
-            if constexpr (f < G * TF) {
-                constexpr int j = f / TF, r = f % TF;
-                if constexpr (r == 0 && j > 0) acch = bias_tile(sb2, th + j);
-                if constexpr (r == NA2) tile_to_frags<GNP>(acch, g.alpha2, hf[0], hf[1]);
-                if constexpr (r < NA2) {
-                    acch = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(p), x4[r / PM], acch, 0, 0, 0);
+            if constexpr (f < TF) {
+                if constexpr (f == NA2) tile_to_frags<GNP>(acch, g.alpha2, hf[0], hf[1]);
+                if constexpr (f < NA2) {
+                    acch = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(p), x4[f / PM], acch, 0, 0, 0);
                 } else {
-                    constexpr int q = (r - NA2) / PM, s_ = q / NM, m = q % NM;
+                    constexpr int q = (f - NA2) / PM, s_ = q / NM, m = q % NM;
                     acc2[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(p), hf[s_], acc2[m], 0, 0, 0);
                 }
             }
         });
     }
-    wait_vm<0>();                                                  // (pieces requested past the end must land before the LDS is released)
+    ring.drain();
 
     // ---- y = alpha3 * acc2 (+ GELU): fp32 planes and / or fp16 k-octets (csrc/gemm_bstat.hip's stores) ----
     const __amdgpu_buffer_rsrc_t rc32 = __builtin_amdgcn_make_buffer_rsrc(
@@ -370,19 +274,16 @@ inline int unit_frags(int n) { return (n + S - 1) / S * S; }
 }  // namespace
 
 // layout of the packed weight stream (the host packs exactly this: ops.PackedTail): total 1-KB fragments (0: shape / product count not
-// built); *stage = fragments per stage (units are padded to multiples of it), *group = hidden tiles per phase-2 unit, *pw_one_unit = 1
-// when the NC pw tiles form ONE unit (padded once) instead of a unit each
+// built); every pw tile and every hidden tile is a unit padded to whole stages: *stage = 16, *group = 1, *pw_one_unit = 0, always
 extern "C" int sf_sk_tail_layout(int C, int H, int M2, int pm, int* stage, int* group, int* pw_one_unit) {
     const Shape* s = find_shape(C, M2);
     if (!s || (pm != 1 && pm != 2) || H <= 0 || H % 32 || H > kMaxH) return 0;
     if (s->NC == 8 && s->NM == 6 && pm == 1) return 0;           // (256 -> H -> 192 with single-product weights spills 8 registers: not built)
-    const int ks = 2 * s->NC, G = tail_group(s->NC, s->NM, pm), nh = H / 32;
-    if (nh % G) return 0;
     if (stage) *stage = S;
-    if (group) *group = G;
-    if (pw_one_unit) *pw_one_unit = SF_TAIL_V2 ? 1 : 0;
-    const int f1 = SF_TAIL_V2 ? unit_frags(s->NC * ks * pm) : s->NC * unit_frags(ks * pm);
-    return f1 + (nh / G) * unit_frags(G * (ks + 2 * s->NM) * pm);
+    if (group) *group = 1;
+    if (pw_one_unit) *pw_one_unit = 0;
+    const int ks = 2 * s->NC;
+    return s->NC * unit_frags(ks * pm) + (H / 32) * unit_frags((ks + 2 * s->NM) * pm);
 }
 
 extern "C" int sf_sk_tail_frags(int C, int H, int M2, int pm) { return sf_sk_tail_layout(C, H, M2, pm, nullptr, nullptr, nullptr); }

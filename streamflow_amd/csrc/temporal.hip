@@ -13,15 +13,12 @@
 //     partial dot products over its 32 channels, two cross-lane steps (lane ^ 16, lane ^ 32) for the other three quarters;
 //   * LayerNorm statistics the same way (in-lane sums over 32 channels + the two cross-lane steps);
 //   * all four layers' weights are ONE host-packed stream of 1-KB fragments in consumption order (256 x PM fragments: 256 / 512 KB),
-//     moved L2 -> LDS by DMA through a ring of 16-KB stages shared by the workgroup's 4 waves (64 pixels), as in ffn_pair.hip.
+//     moved L2 -> LDS by DMA through a ring of 16-KB stages shared by the workgroup's 4 waves (64 pixels): csrc/weight_ring.h.
 // Input: the fp16 k-octet copy of the motion features (the B operand format; also the residual -- the same rounding every other
 // consumer of that tensor sees).  Output: fp32 planes (+ their k-octet copy) into the GRU's input buffer.
 // Arithmetic: the config-2 class (activations enter every product as fp16, PM = 1: fp16 weights, PM = 2: hi + lo; fp32 accumulation,
 // fp32 LayerNorm / softmax / GELU).
-#include "sf_common.h"
-
-#include <cstdlib>
-#include <type_traits>
+#include "weight_ring.h"
 
 namespace {
 
@@ -31,12 +28,13 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr;
 using sf::f32x2;
+using sf::static_for;
+using sf::wait_vm;
 
 constexpr int kC = 128, kH = 256;                          // channels, MLP hidden rows (timm Block, mlp_ratio 2)
 constexpr int kWaves = 4, kThreads = 256, kPxWave = 16, kPxWg = kWaves * kPxWave;
-constexpr int S = 16, kStage = S * 1024, RING = 3, PCS = S / kWaves;
+constexpr int S = 16, kStage = S * 1024, RING = 3;
 constexpr int kOob = 1 << 30;
 
 struct TbArgs {
@@ -44,19 +42,6 @@ struct TbArgs {
     int ntile;            // pixel tiles (64 pixels) per clip
     int64_t w_bytes;
 };
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 // sum over the four lanes (kq = 0 .. 3) that hold the same pixel: lanes l, l ^ 16, l ^ 32, l ^ 48
 __device__ __forceinline__ float quad_sum(float v) {
@@ -97,23 +82,9 @@ __global__ __launch_bounds__(kThreads, 2) void temporal_block_kernel(const TbArg
     const int px = tile * kPxWg + wave * kPxWave + l15;
     const bool pin = px < g.N;
 
-    // ---- the weight stream (ffn_pair.hip's ring): stage s = bytes [16 KB s, 16 KB (s + 1)); wave w moves pieces w, w + 4, ... ----
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.wstream), 0, (int)a.w_bytes, 0x00020000);
-    // (stages requested past the end of the stream -- the loop keeps the request count per trip constant -- re-read the LAST stage
-    // into a slot nobody reads any more: the stage offset travels in the scalar offset, which the raw-buffer range check of gfx9
-    // does not cover, so "out of range: zeros" must not be relied on: ADVICE r5)
-    const int last_stage = (int)(a.w_bytes / kStage) - 1;
-    auto issue_stage = [&](int s, int slot) {
-        const int sc = min(s, last_stage);
-#pragma unroll
-        for (int i = 0; i < PCS; ++i) {
-            const int piece = wave + kWaves * i;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + slot * kStage + piece * 1024), 16, lane * 16,
-                                                     sc * kStage + piece * 1024, 0, 0);
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < RING - 1; ++i) issue_stage(i, i);
+    // ---- the weight stream: stages of 16 KB through the shared ring ----
+    sf::WeightRing<S, RING, kWaves> ring(g.wstream, a.w_bytes, smem, wave, lane);
+    ring.prologue();
 
     if (tid < 128) {
         sp_ln1w[tid] = g.ln1_w[tid]; sp_ln1b[tid] = g.ln1_b[tid];
@@ -169,29 +140,13 @@ __global__ __launch_bounds__(kThreads, 2) void temporal_block_kernel(const TbArg
         }
     }
 
-    int gs = 0, slot = 0;                                         // global stage index, its ring slot
-    auto stage_begin = [&]() -> const char* {
-        issue_stage(gs + RING - 1, slot == 0 ? RING - 1 : slot - 1);      // (past the end: the last stage again -- the counted wait sees the same queue)
-        return smem + slot * kStage + lane * 16;
-    };
-    auto stage_end = [&]() {
-        // every fragment read of the stage has EXECUTED before the barrier (ffn_pair.hip: the refill race)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        wait_vm<PCS * (RING - 2)>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        ++gs;
-        slot = (slot == RING - 1) ? 0 : slot + 1;
-    };
-
     // ---- phase 1: q (row tiles 0 .. 7) and k (8 .. 15) of every frame, kept as fp16 in the accumulator layout ----
     u32x2 qk[16][TT];
     {
         constexpr int TPS = S / FT;                               // tiles per stage
         static_for<0, 16 / TPS>([&](auto j_tag) {
             constexpr int j = decltype(j_tag)::value;
-            const char* sp = stage_begin();
+            const char* sp = ring.begin();
             f32x4 acc[TPS][TT];
 #pragma unroll
             for (int u = 0; u < TPS; ++u)
@@ -207,7 +162,7 @@ __global__ __launch_bounds__(kThreads, 2) void temporal_block_kernel(const TbArg
             for (int u = 0; u < TPS; ++u)
 #pragma unroll
                 for (int t = 0; t < TT; ++t) qk[j * TPS + u][t] = pack4(g.alpha_qkv * acc[u][t]);
-            stage_end();
+            ring.end();
         });
     }
 
@@ -278,7 +233,7 @@ __global__ __launch_bounds__(kThreads, 2) void temporal_block_kernel(const TbArg
         f16x8 of[TT];
         static_for<0, PM>([&](auto st_tag) {
             constexpr int st = decltype(st_tag)::value;
-            const char* sp = stage_begin();
+            const char* sp = ring.begin();
             static_for<0, S>([&](auto i_tag) {
                 constexpr int i = decltype(i_tag)::value, f = st * S + i;
                 if constexpr (f == 2 * FT) {
@@ -305,7 +260,7 @@ __global__ __launch_bounds__(kThreads, 2) void temporal_block_kernel(const TbArg
                     for (int t = 0; t < TT; ++t) xa[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr, of[t], xa[m][t], 0, 0, 0);
                 }
             });
-            stage_end();
+            ring.end();
         });
     }
 
@@ -359,7 +314,7 @@ __global__ __launch_bounds__(kThreads, 2) void temporal_block_kernel(const TbArg
         f16x8 hf[TT];
         static_for<0, PM>([&](auto st_tag) {
             constexpr int st = decltype(st_tag)::value;
-            const char* sp = stage_begin();
+            const char* sp = ring.begin();
             static_for<0, S>([&](auto i_tag) {
                 constexpr int i = decltype(i_tag)::value, f = st * S + i;
                 if constexpr (f == 2 * FT) {
@@ -391,10 +346,10 @@ __global__ __launch_bounds__(kThreads, 2) void temporal_block_kernel(const TbArg
                     for (int t = 0; t < TT; ++t) xa[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr, hf[t], xa[m][t], 0, 0, 0);
                 }
             });
-            stage_end();
+            ring.end();
         });
     }
-    wait_vm<0>();                                                  // (pieces requested past the end must land before the LDS is released)
+    ring.drain();
 
     // ---- out = alpha_fc2 * acc: fp32 planes and / or their k-octet copy; lane parts of the address in the vector offset ----
     const int v16 = ((kq >> 1) * (int)g.ldy16 + px) * 16 + 8 * (kq & 1);

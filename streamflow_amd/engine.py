@@ -509,29 +509,23 @@ class HotPathEngine:
         # layers whose weights are used as ONE fp16 value in the f16x2 mode (see presets.py: chosen by measured EPE)
         self.single_layers = tuple(single_layers or ())
         self.W.set_single("all" if self.single_layers == ("all",) else self.single_layers)
-        # the FFN pairs' weight streams are built NOW (device-synchronous), not lazily inside a forward: a forward enqueues on several
-        # streams (and may be a graph capture) -- a stream built on one of them would be read by another before it exists
-        if (self.options.ffn_pairs or self.options.sk_tail) and self.precision in (ops.PRECISION_F16X2, ops.PRECISION_F16):
+        # the fused chain kernels' weight streams are built NOW (device-synchronous), not lazily inside a forward: a forward enqueues
+        # on several streams (and may be a graph capture) -- a stream built on one of them would be read by another before it exists
+        if self.precision in (ops.PRECISION_F16X2, ops.PRECISION_F16):
+            o, blocks, packs = self.options, [getattr(self.W, b) for b in HotPathWeights.SK_BLOCKS], []
+            if o.ffn_pairs:
+                packs += [pair for blk in blocks for pair in (blk.pair1, blk.pair2)]
+            if o.sk_tail:
+                packs += [blk.tail for blk in blocks]
+            if o.mask_upsample:
+                packs.append(self.W.mask_pack)
+            if o.temporal_block:
+                packs.append(self.W.temporal)
             cxp = ops.Ctx(precision=self.precision)
             with torch.cuda.device(self.device):
-                for b in HotPathWeights.SK_BLOCKS:
-                    blk = getattr(self.W, b)
-                    for pair in (blk.pair1, blk.pair2) if self.options.ffn_pairs else ():
-                        if (pair.K1, pair.M2) in ops.PAIR_SHAPES[0] | ops.PAIR_SHAPES[1]:
-                            pair.stream(*pair.products(cxp))
-                    if self.options.sk_tail and blk.tail.built(blk.tail.products(cxp)):
-                        blk.tail.stream(blk.tail.products(cxp))
+                for p in packs:
+                    p.prebuild(cxp)
                 torch.cuda.synchronize(self.device)
-        if self.options.mask_upsample and self.precision in (ops.PRECISION_F16X2, ops.PRECISION_F16) and self.W.mask_pack.built():
-            with torch.cuda.device(self.device):
-                self.W.mask_pack.stream(self.W.mask_pack.products(ops.Ctx(precision=self.precision)))
-                torch.cuda.synchronize(self.device)
-        if self.options.temporal_block and self.precision in (ops.PRECISION_F16X2, ops.PRECISION_F16) and self.W.temporal.built():
-            pm = self.W.temporal.products(ops.Ctx(precision=self.precision))
-            if pm is not None:
-                with torch.cuda.device(self.device):
-                    self.W.temporal.stream(pm)
-                    torch.cuda.synchronize(self.device)
         self.use_graph = use_graph
         self._plans: Dict[Tuple[int, int, int, int], _Plan] = {}
         self.max_plans = int(self.options.max_plans)

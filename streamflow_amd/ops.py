@@ -316,23 +316,26 @@ class PackedLinear:
         self.split_error = float(((hi.float() + lo.float()) - wm).abs().max() / max(wmax * self.split_scale, 1e-30))
 
 
-class PackedPair:
-    """The two 1x1 convolutions of an SK block's FFN (update.py:14-16: conv -> GELU -> conv) as ONE weight stream for
-    sf_ffn_pair (csrc/ffn_pair.hip): 1-KB MFMA fragments in consumption order, built per (products of layer 1, products of
-    layer 2) on first use.  `first` / `second` are the layers' PackedLinear objects (their `single` flags, scales and biases
-    are the source of truth: the pair computes exactly what the two sf_gemm launches compute)."""
+def _bias_ptr(A: "PackedLinear") -> Optional[int]:
+    """Device address of a layer's pre-scaled bias (None: no bias)."""
+    return None if A.bias_split is None else A.bias_split.data_ptr()
 
-    S = 16                                               # fragments per stage (csrc/ffn_pair.hip)
 
-    def __init__(self, first: "PackedLinear", second: "PackedLinear"):
-        assert first.M == second.K and not first.conv3x3 and not second.conv3x3
-        self.first, self.second = first, second
-        self.K1, self.H, self.M2 = first.K, first.M, second.M
+def _shared_products(layers, cx: "Ctx") -> Optional[int]:
+    """MFMA products per weight where a kernel takes ONE value for all its layers: 1 (fp16 weights) or 2 (hi + lo); a layer set that
+    mixes the two keeps the unfused launches (None)."""
+    if cx.precision == PRECISION_F16 or all(l.single for l in layers):
+        return 1
+    return 2 if not any(l.single for l in layers) else None
+
+
+class _PackedStream:
+    """What the weight streams of the fused chain kernels share (csrc/weight_ring.h is their consumer): one stream per product
+    count(s), built on first use and kept; never inside a graph capture; (hi, lo) fp16 images of split_scale * W.  A subclass adds
+    its fragment order (`stream`) and which stream a context asks for (`prebuild`)."""
+
+    def __init__(self):
         self._streams = {}
-
-    def products(self, cx: "Ctx"):
-        one = cx.precision == PRECISION_F16
-        return (1 if (one or self.first.single) else 2), (1 if (one or self.second.single) else 2)
 
     @staticmethod
     def _split(A: "PackedLinear", rows: int, cols: int):
@@ -342,13 +345,44 @@ class PackedPair:
         hi = w.to(torch.float16)
         return hi, (w - hi.float()).to(torch.float16)
 
+    def _cached(self, key, pack) -> torch.Tensor:
+        """The stream of `key`, packed by pack() on first use.  A forward enqueues on several streams and may be a graph capture: a
+        stream built inside one would be read by another before it exists, so the first use must come earlier (prebuild)."""
+        st = self._streams.get(key)
+        if st is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}.stream: weight stream requested for the first time inside a graph capture; "
+                                   "build it before (HotPathEngine does at construction)")
+            st = self._streams[key] = pack()
+        return st
+
+
+class PackedPair(_PackedStream):
+    """The two 1x1 convolutions of an SK block's FFN (update.py:14-16: conv -> GELU -> conv) as ONE weight stream for
+    sf_ffn_pair (csrc/ffn_pair.hip): 1-KB MFMA fragments in consumption order, built per (products of layer 1, products of
+    layer 2) on first use.  `first` / `second` are the layers' PackedLinear objects (their `single` flags, scales and biases
+    are the source of truth: the pair computes exactly what the two sf_gemm launches compute)."""
+
+    S = 16                                               # fragments per stage (csrc/ffn_pair.hip)
+
+    def __init__(self, first: "PackedLinear", second: "PackedLinear"):
+        assert first.M == second.K and not first.conv3x3 and not second.conv3x3
+        super().__init__()
+        self.first, self.second = first, second
+        self.K1, self.H, self.M2 = first.K, first.M, second.M
+
+    def products(self, cx: "Ctx"):
+        one = cx.precision == PRECISION_F16
+        return (1 if (one or self.first.single) else 2), (1 if (one or self.second.single) else 2)
+
+    def prebuild(self, cx: "Ctx") -> None:
+        if (self.K1, self.M2) in PAIR_SHAPES[0] | PAIR_SHAPES[1]:
+            self.stream(*self.products(cx))
+
     def stream(self, pm1: int, pm2: int) -> torch.Tensor:
-        key = (pm1, pm2)
-        if key in self._streams:
-            return self._streams[key]
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("PackedPair.stream: weight stream requested for the first time inside a graph capture; build it "
-                               "before (HotPathEngine does at construction)")
+        return self._cached((pm1, pm2), lambda: self._pack(pm1, pm2))
+
+    def _pack(self, pm1: int, pm2: int) -> torch.Tensor:
         nk1, nt2, hp = (self.K1 + 31) // 32, (self.M2 + 15) // 16, (self.H + 31) // 32
         fpad = int(_lib.load().sf_ffn_pair_frags(self.K1, self.M2, pm1, pm2))
         h1, l1 = self._split(self.first, hp * 32, nk1 * 32)
@@ -369,11 +403,10 @@ class PackedPair:
         pad = torch.zeros(hp, fpad - f1.shape[1] - f2.shape[1], 64 * 8, dtype=torch.float16, device=dev)
         st = torch.cat([f1, f2, pad], dim=1).contiguous().view(-1)
         assert st.numel() * 2 == hp * fpad * 1024
-        self._streams[key] = st
         return st
 
 
-class PackedTail:
+class PackedTail(_PackedStream):
     """The back half of an SK block -- pw (residual folded: W + I), ffn2.0, ffn2.2 (update.py:35-36, :14-16) -- as ONE weight stream for
     sf_sk_tail (csrc/sk_tail.hip): 1-KB fragments of 32 rows x 16 k in consumption order, units padded to 16-fragment stages (layout:
     include/streamflow_hip.h).  The PackedLinear objects stay the source of truth (rounding, power-of-two scales, biases, `single`)."""
@@ -382,31 +415,31 @@ class PackedTail:
 
     def __init__(self, pw_res: "PackedLinear", f0: "PackedLinear", f2: "PackedLinear"):
         assert pw_res.M == pw_res.K == f0.K and f0.M == f2.K and not (pw_res.conv3x3 or f0.conv3x3 or f2.conv3x3)
+        super().__init__()
         self.layers = (pw_res, f0, f2)
         self.C, self.H, self.M2 = pw_res.K, f0.M, f2.M
-        self._streams = {}
 
     def products(self, cx: "Ctx") -> Optional[int]:
-        """MFMA products per weight: 1 or 2 -- the kernel takes ONE value for the three layers; a mixed set keeps the three launches."""
-        if cx.precision == PRECISION_F16 or all(l.single for l in self.layers):
-            return 1
-        return 2 if not any(l.single for l in self.layers) else None
+        return _shared_products(self.layers, cx)
 
     def built(self, pm: Optional[int]) -> bool:
         return pm is not None and int(_lib.load().sf_sk_tail_frags(self.C, self.H, self.M2, pm)) > 0
 
+    def prebuild(self, cx: "Ctx") -> None:
+        pm = self.products(cx)
+        if self.built(pm):
+            self.stream(pm)
+
     def stream(self, pm: int) -> torch.Tensor:
-        if pm in self._streams:
-            return self._streams[pm]
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("PackedTail.stream: weight stream requested for the first time inside a graph capture; build it before "
-                               "(HotPathEngine does at construction)")
+        return self._cached(pm, lambda: self._pack(pm))
+
+    def _pack(self, pm: int) -> torch.Tensor:
         nc, nh, nm = (self.C + 31) // 32, self.H // 32, (self.M2 + 31) // 32
         ks = 2 * nc
         stage, group, one = C.c_int(0), C.c_int(0), C.c_int(0)
         total = int(_lib.load().sf_sk_tail_layout(self.C, self.H, self.M2, pm, C.byref(stage), C.byref(group), C.byref(one)))
-        assert total > 0 and nh % group.value == 0
-        w1, w2, w3 = (PackedPair._split(l, r, c) for l, (r, c) in zip(self.layers, ((nc * 32, nc * 32), (nh * 32, nc * 32), (nm * 32, nh * 32))))
+        assert total > 0 and (stage.value, group.value, one.value) == (self.S, 1, 0)   # every tile a unit of its own, padded to a stage
+        w1, w2, w3 = (self._split(l, r, c) for l, (r, c) in zip(self.layers, ((nc * 32, nc * 32), (nh * 32, nc * 32), (nm * 32, nh * 32))))
         dev = w1[0].device
         khalf = torch.arange(2, device=dev).view(2, 1)
         i = torch.arange(8, device=dev).view(1, 8)
@@ -420,26 +453,22 @@ class PackedTail:
                 out.append(plane[r0:r0 + 32][:, cols].reshape(32, 2, 8).permute(1, 0, 2).reshape(512))
 
         def pad():
-            while (len(out) % stage.value) != 0:
+            while len(out) % self.S:
                 out.append(zero)
 
         for t in range(nc):                                                            # phase 1: pw row tiles over the natural k-steps
             for k in range(ks):
                 emit(w1, 32 * t, 16 * k + natural)
-            if not one.value:
-                pad()
-        pad()
-        for th in range(nh):                                                           # phase 2: per 32 hidden rows, `group` tiles per unit
+            pad()
+        for th in range(nh):                                                           # phase 2: per 32 hidden rows
             for k in range(ks):                                                        # ffn2.0 over x4 (k-step = (tile k / 2, half k % 2))
                 emit(w2, 32 * th, 32 * (k // 2) + 16 * (k % 2) + acc_order)
             for s_ in range(2):                                                        # ffn2.2's two k-steps from this hidden tile
                 for m in range(nm):
                     emit(w3, 32 * m, 32 * th + 16 * s_ + acc_order)
-            if (th + 1) % group.value == 0:
-                pad()
+            pad()
         st = torch.cat(out).contiguous()
-        assert st.numel() == int(_lib.load().sf_sk_tail_frags(self.C, self.H, self.M2, pm)) * 512, (st.numel() // 512, self.C, self.H, self.M2, pm)
-        self._streams[pm] = st
+        assert st.numel() == total * 512, (st.numel() // 512, self.C, self.H, self.M2, pm)
         return st
 
 
@@ -468,9 +497,7 @@ def sk_tail(tail: PackedTail, X: Planes, Y: Planes, gelu_out: bool = False, cx: 
     g = _lib.SfSkTail()
     g.X, g.strideX, g.ldx = X.ptr, X.img_stride, X.P
     g.wstream, g.wstream_bytes = st.data_ptr(), st.numel() * 2
-    g.bias1 = None if A1.bias_split is None else A1.bias_split.data_ptr()
-    g.bias2 = None if A2.bias_split is None else A2.bias_split.data_ptr()
-    g.bias3 = None if A3.bias_split is None else A3.bias_split.data_ptr()
+    g.bias1, g.bias2, g.bias3 = _bias_ptr(A1), _bias_ptr(A2), _bias_ptr(A3)
     g.alpha1, g.alpha2, g.alpha3 = 1.0 / A1.split_scale, 1.0 / A2.split_scale, 1.0 / A3.split_scale
     g.N, g.batch, g.C, g.H, g.M2, g.pm, g.gelu_out = X.P, X.n_img, tail.C, tail.H, tail.M2, pm, int(bool(gelu_out))
     out_bytes = 2.0
@@ -493,15 +520,15 @@ def sk_tail(tail: PackedTail, X: Planes, Y: Planes, gelu_out: bool = False, cx: 
         refresh_shadow(Y, cx)
 
 
-class PackedTemporal:
+class PackedTemporal(_PackedStream):
     """The four contractions of the temporal transformer block (update.py:459-484 -> timm Block: qkv, proj, fc1, fc2) as ONE weight
     stream for sf_temporal_block (csrc/temporal.hip): 1-KB MFMA fragments in consumption order (layout: include/streamflow_hip.h).
     The PackedLinear objects stay the source of truth (rounding, power-of-two scales, biases, `single` flags)."""
 
     def __init__(self, qkv: "PackedLinear", proj: "PackedLinear", fc1: "PackedLinear", fc2: "PackedLinear"):
+        super().__init__()
         self.layers = (qkv, proj, fc1, fc2)
         self.C, self.H = qkv.K, fc1.M
-        self._streams = {}
 
     def built(self) -> bool:
         qkv, proj, fc1, fc2 = self.layers
@@ -509,19 +536,18 @@ class PackedTemporal:
                 fc1.K == 128 and (fc2.M, fc2.K) == (128, 256) and not any(l.conv3x3 for l in self.layers))
 
     def products(self, cx: "Ctx") -> Optional[int]:
-        """MFMA products per element: 1 (fp16 weights) or 2 (hi + lo) -- the kernel takes ONE value for the block; a layer set that
-        mixes the two keeps the unfused launches (None)."""
-        if cx.precision == PRECISION_F16 or all(l.single for l in self.layers):
-            return 1
-        return 2 if not any(l.single for l in self.layers) else None
+        return _shared_products(self.layers, cx)
+
+    def prebuild(self, cx: "Ctx") -> None:
+        pm = self.products(cx)
+        if self.built() and pm is not None:
+            self.stream(pm)
 
     def stream(self, pm: int) -> torch.Tensor:
-        if pm in self._streams:
-            return self._streams[pm]
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("PackedTemporal.stream: weight stream requested for the first time inside a graph capture; build it "
-                               "before (HotPathEngine does at construction)")
-        qkv, proj, fc1, fc2 = (PackedPair._split(l, l.M, l.K) for l in self.layers)       # (hi, lo) of scale * W, [M, K] fp16
+        return self._cached(pm, lambda: self._pack(pm))
+
+    def _pack(self, pm: int) -> torch.Tensor:
+        qkv, proj, fc1, fc2 = (self._split(l, l.M, l.K) for l in self.layers)       # (hi, lo) of scale * W, [M, K] fp16
         dev = qkv[0].device
         kq = torch.arange(4, device=dev).view(4, 1)
         i = torch.arange(8, device=dev).view(1, 8)
@@ -552,17 +578,16 @@ class PackedTemporal:
                 emit(fc2, m, h, True)
         st = torch.cat(out).contiguous()
         assert st.numel() == int(_lib.load().sf_temporal_block_frags(pm)) * 512
-        self._streams[pm] = st
         return st
 
 
-class PackedMask:
+class PackedMask(_PackedStream):
     """mask.2 (update.py:758: Conv1x1 256 -> 576) as the weight stream of sf_mask_upsample (csrc/mask_upsample.hip): row tile 0 .. 35,
     k-step 0 .. 7, `lo` before `hi`."""
 
     def __init__(self, layer: "PackedLinear"):
+        super().__init__()
         self.layer = layer
-        self._streams = {}
 
     def built(self) -> bool:
         return (self.layer.M, self.layer.K) == (576, 256) and not self.layer.conv3x3
@@ -570,17 +595,19 @@ class PackedMask:
     def products(self, cx: "Ctx") -> int:
         return 1 if (cx.precision == PRECISION_F16 or self.layer.single) else 2
 
+    def prebuild(self, cx: "Ctx") -> None:
+        if self.built():
+            self.stream(self.products(cx))
+
     def stream(self, pm: int) -> torch.Tensor:
-        if pm in self._streams:
-            return self._streams[pm]
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("PackedMask.stream: weight stream requested for the first time inside a graph capture")
-        hi, lo = PackedPair._split(self.layer, 576, 256)
+        return self._cached(pm, lambda: self._pack(pm))
+
+    def _pack(self, pm: int) -> torch.Tensor:
+        hi, lo = self._split(self.layer, 576, 256)
         planes = [lo, hi] if pm == 2 else [hi]
         f = torch.stack([w.view(36, 16, 8, 4, 8) for w in planes], dim=0)                   # [plane, tile, row, s, kq, i]
         st = f.permute(1, 3, 0, 4, 2, 5).reshape(-1).contiguous()                           # [tile][s][plane][(kq, row), i]
         assert st.numel() == int(_lib.load().sf_mask_upsample_frags(pm)) * 512
-        self._streams[pm] = st
         return st
 
 
@@ -603,7 +630,7 @@ def mask_upsample(pack: PackedMask, M256: Planes, flow: torch.Tensor, out: torch
     g = _lib.SfMaskUpsample()
     g.X16, g.strideX, g.ldx = sh.ptr, sh.img_stride, sh.P
     g.wstream, g.wstream_bytes = st.data_ptr(), st.numel() * 2
-    g.bias = None if A.bias_split is None else A.bias_split.data_ptr()
+    g.bias = _bias_ptr(A)
     g.flow, g.out = flow.data_ptr(), out.data_ptr()
     g.n_img, g.h, g.w, g.K, g.M, g.pm = M256.n_img, h, w, 256, 576, pm
     g.alpha = 0.25 / A.split_scale
@@ -637,9 +664,7 @@ def temporal_block(pack: PackedTemporal, X: Planes, Y: Planes, TT: int, ln1, ln2
     g.X16, g.strideX, g.ldx = sh.ptr, sh.img_stride, sh.P
     g.wstream, g.wstream_bytes = st.data_ptr(), st.numel() * 2
     g.ln1_w, g.ln1_b, g.ln2_w, g.ln2_b = ln1[0].data_ptr(), ln1[1].data_ptr(), ln2[0].data_ptr(), ln2[1].data_ptr()
-    g.bias_proj = None if proj.bias_split is None else proj.bias_split.data_ptr()
-    g.bias_fc1 = None if fc1.bias_split is None else fc1.bias_split.data_ptr()
-    g.bias_fc2 = None if fc2.bias_split is None else fc2.bias_split.data_ptr()
+    g.bias_proj, g.bias_fc1, g.bias_fc2 = _bias_ptr(proj), _bias_ptr(fc1), _bias_ptr(fc2)
     g.Y, g.strideY, g.ldy = Y.ptr, Y.img_stride, Y.P
     nbytes = 2.0 + 4.0
     if Y.shadow is not None and cx.shadows:
@@ -688,8 +713,7 @@ def ffn_pair(pair: PackedPair, X: Planes, Y: Planes, mode: int, dw_w: Optional[t
     g.x_group, g.x_group_stride = src.group, src.group_stride
     g.wstream, g.wstream_bytes = st.data_ptr(), st.numel() * 2
     A1, A2 = pair.first, pair.second
-    g.bias1 = None if A1.bias_split is None else A1.bias_split.data_ptr()
-    g.bias2 = None if A2.bias_split is None else A2.bias_split.data_ptr()
+    g.bias1, g.bias2 = _bias_ptr(A1), _bias_ptr(A2)
     g.alpha1, g.alpha2 = 1.0 / A1.split_scale, 1.0 / A2.split_scale
     g.N, g.batch, g.K1, g.H, g.M2 = X.P, X.n_img, pair.K1, pair.H, pair.M2
     g.pm1, g.pm2, g.mode, g.gelu_out = pm1, pm2, int(mode), int(bool(gelu_out))
@@ -817,7 +841,7 @@ def gemm(A: PackedLinear, X: Planes, Y: Planes, epilogue: int = EPI_NONE, R: Opt
         g.A_hi, g.A_lo, g.lda_h, g.a_k_pad = A.hi.data_ptr(), A.lo.data_ptr(), A.lda_h, A.k_pad
         # the split image holds split_scale * W: C = alpha/s * (s W X + s b)
         alpha = alpha / A.split_scale
-        g.bias = None if A.bias_split is None else A.bias_split.data_ptr()
+        g.bias = _bias_ptr(A)
     g.b_group, g.b_group_stride = X.group, X.group_stride
     if R is not None:
         assert R.rows == A.M and R.n_img == Y.n_img
