@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 124
+#define SF_VERSION 125
 
 enum {
     SF_OK = 0,
@@ -631,6 +631,40 @@ enum {
 #define SF_SCORE_WS_BYTES (1024 * SF_SCORE_LEN * 8)
 int sf_flow_score(const float* pred, int64_t pred_ch_stride, int64_t pred_row_stride, const float* gt, int gt_h, int gt_w,
                   int step, int h, int w, double* acc, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- video clips: uint8 frames -> clip batches, per-pair outputs -> flows in video order (demo.py:502-534) ---------------------
+ * The clip schedule of the reference's read_video_and_group_predict, in closed form (streamflow_amd.demo.group_clips states the
+ * same thing as a list): a video of n frames in clips of T has nc = ceil((n - 1) / (T - 1)) clips; clip c starts at frame
+ * s(c) = min(c (T - 1), n - T); pair j (frames j -> j + 1, 0 <= j < n - 1) belongs to clip c(j) = min(j / (T - 1), nc - 1) and is
+ * that clip's slot j - s(c(j)).  Only the last clip can overlap its predecessor; the slots it repeats belong to the earlier clip.
+ * Both entry points compute the schedule in the kernel: no table is uploaded, one launch each, no host synchronisation.
+ *
+ * sf_frames_to_clips: `frames` holds the frames frame0 .. frame0 + n_buf - 1 of the video as uint8, byte (f, y, x, ch) at
+ *   frames + (f - frame0) frame_stride + y row_stride + x px_stride + ch ch_stride (strides in bytes, >= 0: HWC is (3 H W, 3 W, 3, 1),
+ *   CHW is (3 H W, W, 1, H W), views of larger buffers are fine).  For the clips first_clip .. first_clip + n_clips - 1:
+ *     out[c'][t][ch][y][x] = lut[ frame s(first_clip + c') + t at (clamp(y - pad_top, 0, H - 1), clamp(x - pad_left, 0, W - 1), ch) ]
+ *   out fp32 [n_clips][T][3][Hp][Wp], 16-byte aligned; lut: DEVICE table of 256 floats (the normalisation, built by the caller with
+ *   the model's own expression, so the kernel does no arithmetic on pixel values).  SF_ERR_BAD_ARG before any launch for: null
+ *   pointers, T < 2, n < T, clips outside 0 .. nc - 1, a clip whose frames fall outside the buffer, Hp / Wp not multiples of 8 or
+ *   smaller than the frame plus pad, negative strides, n_clips T > 65535, Hp Wp >= 2^30, a misaligned out.
+ *
+ * sf_clips_to_flows: pairs->p[k] is the model's output for slot k of every clip of the batch, [n_clips][2][Hp][Wp] addressed as
+ *   p[k] + c' clip_stride + ch ch_stride + y row_stride + x (strides in floats; all slots share them).  For the pairs
+ *   pair0 .. pair0 + n_pairs - 1 of the video:  out[j - pair0][ch][y][x] = p[j - s(c(j))][c(j) - first_clip][ch][y + pad_top][x + pad_left]
+ *   out fp32 [n_pairs][2][H][W] contiguous.  float4 accesses where strides, pad_left, W and the pointers allow, scalar otherwise.
+ *   SF_ERR_UNSUPPORTED for T - 1 > SF_VIDEO_MAX_PAIRS; SF_ERR_BAD_ARG for null pointers (pairs->p[0 .. T - 2] included), T < 2,
+ *   n < T, pairs outside 0 .. n - 2, a pair whose clip is outside first_clip .. first_clip + n_clips - 1, row_stride < W + pad_left,
+ *   n_pairs > 32767. */
+#define SF_VIDEO_MAX_PAIRS 8
+typedef struct SfPairPtrs {
+    const float* p[SF_VIDEO_MAX_PAIRS];
+} SfPairPtrs;
+int sf_frames_to_clips(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, int64_t px_stride, int64_t ch_stride,
+                       int frame0, int n_buf, int n, int T, int first_clip, int n_clips, int H, int W, int pad_top, int pad_left,
+                       int Hp, int Wp, const float* lut, float* out, void* stream);
+int sf_clips_to_flows(const SfPairPtrs* pairs, int64_t clip_stride, int64_t ch_stride, int64_t row_stride, int n, int T,
+                      int first_clip, int n_clips, int pair0, int n_pairs, int H, int W, int pad_top, int pad_left, float* out,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -104,3 +104,61 @@ def vis_flow(flows_result: Sequence[torch.Tensor], save_dir: str = "flow_result"
         paths.append(os.path.join(save_dir, "frame_%04d.png" % i))
         flow_io.write_png(paths[-1], img)
     return paths
+
+
+def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, clips_per_step: int = 8, mode: str = "sintel",
+                                  save_dir: str = None, flo_dir: str = None, rad_max=None) -> int:
+    """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames: video.FrameDir ->
+    StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
+    are coloured on the GPU and written as ``save_dir/frame_%04d.png`` (numbered by pair) and, with `flo_dir`, as Middlebury
+    ``flo_dir/frame_%04d.flo``.  Runs on the current GPU.  Returns the number of pairs."""
+    import os
+    from . import flow_io, video
+    from .model import StreamFlowT4
+    frames = video.FrameDir(path)
+    if not torch.cuda.is_available():
+        raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = StreamFlowT4(ckpt).to(device).eval()
+    for d in (save_dir, flo_dir):
+        if d:
+            os.makedirs(d, exist_ok=True)
+    written = [0]
+
+    def sink(first_pair: int, flows: torch.Tensor) -> None:
+        images = colour_images(list(flows), rad_max=rad_max) if save_dir else []
+        host = flows.cpu().numpy() if flo_dir else None
+        for k in range(flows.shape[0]):
+            name = "frame_%04d" % (first_pair + k)
+            if save_dir:
+                flow_io.write_png(os.path.join(save_dir, name + ".png"), images[k])
+            if flo_dir:
+                flow_io.write_flo(os.path.join(flo_dir, name + ".flo"), host[k].transpose(1, 2, 0))
+        written[0] += int(flows.shape[0])
+
+    video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink)
+    return written[0]
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m streamflow_amd.demo",
+                                 description="Flow fields of a directory of PNG frames, as colour-wheel PNGs (and .flo files)")
+    ap.add_argument("--frames", required=True, help="directory of PNG frames (sorted by name)")
+    ap.add_argument("--ckpt", required=True, help="StreamFlow checkpoint")
+    ap.add_argument("--out", required=True, help="directory for frame_%%04d.png")
+    ap.add_argument("--flo", default=None, help="directory for frame_%%04d.flo")
+    ap.add_argument("--T", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=15)
+    ap.add_argument("--clips-per-step", type=int, default=8)
+    ap.add_argument("--mode", default="sintel", choices=("sintel", "kitti"))
+    ap.add_argument("--rad-max", type=float, default=None, help="one colour scale for the whole video (default: per frame)")
+    a = ap.parse_args(argv)
+    n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
+                                      save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max)
+    print(f"{n} flow fields -> {a.out}" + (f", {a.flo}" if a.flo else ""))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

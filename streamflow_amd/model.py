@@ -150,6 +150,14 @@ class SKFlow_MF8(nn.Module):
         out = ops.tile_blend(flows, tiling.tile_weights((th, tw), sigma, imgs.device), plan, n_clips=B)
         return [out[:, i] for i in range(P)]
 
+    default_iters = 12         # `iters` of forward() (StreamFlowT4: 15)
+
+    @torch.no_grad()
+    def forward_normalised(self, imgs: torch.Tensor, iters: Optional[int] = None) -> List[torch.Tensor]:
+        """Test-mode forward on a clip batch that is ALREADY normalised and padded: imgs fp32 [B, T, 3, H, W] in [-1, 1], H and W
+        multiples of 8 (what ops.frames_to_clips writes) -> T - 1 flows [B, 2, H, W].  `iters=None`: the class's default."""
+        return self._forward_normalised(imgs, self.default_iters if iters is None else int(iters), None, True)
+
     def _forward_normalised(self, imgs: torch.Tensor, iters: int, flow_init, test_mode: bool):
         B, T, C, H, W = imgs.shape
         if H % 8 or W % 8:
@@ -191,6 +199,8 @@ class StreamFlowT4(SKFlow_MF8):
                 self.load_state_dict(hot, strict=False)
         for p in self.parameters():
             p.requires_grad = False
+
+    default_iters = 15
 
     @torch.no_grad()
     def forward(self, images: torch.Tensor, iters: int = 15, flow_init=None, upsample: bool = True,

@@ -1277,6 +1277,99 @@ def flow_score(pred: torch.Tensor, gt: torch.Tensor, acc: torch.Tensor, step: in
                                          _lib.stream()), "sf_flow_score")
 
 
+_NORM_LUT = {}            # device -> the normalisation table of frames_to_clips
+
+
+def norm_lut(device) -> torch.Tensor:
+    """The 256 floats a byte value maps to, built once per device ON that device with the model's own expression
+    (SKFlow_MF8.forward, reference streamflow.py:102: 2 * (x / 255.0) - 1.0): whatever the device's division by a scalar rounds to,
+    the table holds exactly what the model computes from the same byte value."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"norm_lut: the table is built on the GPU it is used on (got {device}); there is no CPU fallback")
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _NORM_LUT:
+        _NORM_LUT[key] = (2 * (torch.arange(256, device=device).float() / 255.0) - 1.0).contiguous()
+    return _NORM_LUT[key]
+
+
+@on_tensor_device
+def frames_to_clips(frames: torch.Tensor, n: int, T: int, first_clip: int, n_clips: int, pad: Sequence[int] = (0, 0, 0, 0),
+                    frame0: int = 0, channels_last: Optional[bool] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 frames -> the normalised, replicate-padded clip batch the encoders take (sf_frames_to_clips, one launch): frames uint8
+    on the GPU, [n_buf, H, W, 3] or [n_buf, 3, H, W] (any strides; `channels_last` decides when both readings fit, default: HWC if
+    the last dimension is 3), holding the frames frame0 .. frame0 + n_buf - 1 of a video of `n` frames; pad = [left, right, top,
+    bottom] as InputPadder._pad.  Returns fp32 [n_clips, T, 3, Hp, Wp] for the clips first_clip .. first_clip + n_clips - 1 of the
+    schedule in include/streamflow_hip.h (= demo.group_clips).  Enqueued on the current stream, no synchronisation."""
+    if not frames.is_cuda:
+        raise RuntimeError(f"frames_to_clips: frames must be on the GPU (got {frames.device}); there is no CPU fallback")
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise RuntimeError(f"frames_to_clips: frames must be uint8 [n, H, W, 3] or [n, 3, H, W] (got {frames.dtype} {tuple(frames.shape)})")
+    if channels_last is None:
+        channels_last = frames.shape[3] == 3
+    if frames.shape[3 if channels_last else 1] != 3:
+        raise RuntimeError(f"frames_to_clips: no channel dimension of 3 in {tuple(frames.shape)} (channels_last={channels_last})")
+    fs = frames.stride(0)
+    if channels_last:
+        (H, W), (rs, ps, cs) = frames.shape[1:3], frames.stride()[1:]
+    else:
+        (H, W), (cs, rs, ps) = frames.shape[2:], frames.stride()[1:]
+    left, right, top, bottom = (int(p) for p in pad)
+    Hp, Wp = int(H) + top + bottom, int(W) + left + right
+    shape = (int(n_clips), int(T), 3, Hp, Wp)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != frames.device or not out.is_contiguous():
+        raise RuntimeError(f"frames_to_clips: out must be contiguous fp32 {shape} on {frames.device} "
+                           f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+    lut = norm_lut(frames.device)
+    _lib.check(_lib.load().sf_frames_to_clips(frames.data_ptr(), fs, rs, ps, cs, int(frame0), int(frames.shape[0]), int(n), int(T),
+                                              int(first_clip), int(n_clips), int(H), int(W), top, left, Hp, Wp, lut.data_ptr(),
+                                              out.data_ptr(), _lib.stream()), "sf_frames_to_clips")
+    return out
+
+
+@on_tensor_device
+def clips_to_flows(pairs: Sequence[torch.Tensor], n: int, T: int, first_clip: int, pair0: int, n_pairs: int, hw: Sequence[int],
+                   pad: Sequence[int] = (0, 0, 0, 0), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The model's T - 1 per-pair outputs of one clip batch -> flow fields in video order (sf_clips_to_flows, one launch): pairs[k]
+    fp32 [n_clips, 2, Hp, Wp] on the GPU with contiguous rows (views of larger buffers are fine; all k share shape and strides), the
+    batch starting at clip `first_clip` of a video of `n` frames.  Returns (or fills `out`, contiguous) fp32 [n_pairs, 2, H, W] =
+    the pairs pair0 .. pair0 + n_pairs - 1, cropped by pad = [left, right, top, bottom]; the duplicates of the tail clip are dropped.
+    Enqueued on the current stream, no synchronisation."""
+    pairs = list(pairs)
+    if len(pairs) != T - 1 or T < 2:
+        raise RuntimeError(f"clips_to_flows: {len(pairs)} pair tensors for clips of T = {T}")
+    if T - 1 > len(_lib.SfPairPtrs().p):
+        raise RuntimeError(f"clips_to_flows: {T - 1} pairs per clip (at most {len(_lib.SfPairPtrs().p)})")
+    p0 = pairs[0]
+    for p in pairs:
+        if not p.is_cuda or p.device != p0.device:
+            raise RuntimeError(f"clips_to_flows: pair tensors must be on one GPU (got {p.device}); there is no CPU fallback")
+        if p.dtype != torch.float32 or p.dim() != 4 or p.shape[1] != 2 or p.stride(3) != 1:
+            raise RuntimeError(f"clips_to_flows: a pair tensor must be fp32 [n_clips, 2, Hp, Wp] with contiguous rows "
+                               f"(got {p.dtype} {tuple(p.shape)}, strides {p.stride()})")
+        if p.shape != p0.shape or p.stride() != p0.stride():
+            raise RuntimeError("clips_to_flows: the pair tensors differ in shape or strides")
+    H, W = int(hw[0]), int(hw[1])
+    left, right, top, bottom = (int(p) for p in pad)
+    if (H + top + bottom, W + left + right) != tuple(p0.shape[2:]):
+        raise RuntimeError(f"clips_to_flows: {H} x {W} plus pad {list(pad)} is not the pair tensors' {tuple(p0.shape[2:])}")
+    shape = (int(n_pairs), 2, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=p0.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != p0.device or not out.is_contiguous():
+        raise RuntimeError(f"clips_to_flows: out must be contiguous fp32 {shape} on {p0.device} "
+                           f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+    ptrs = _lib.SfPairPtrs()
+    for k, p in enumerate(pairs):
+        ptrs.p[k] = p.data_ptr()
+    _lib.check(_lib.load().sf_clips_to_flows(C.byref(ptrs), p0.stride(0), p0.stride(1), p0.stride(2), int(n), int(T), int(first_clip),
+                                             int(p0.shape[0]), int(pair0), int(n_pairs), H, W, top, left, out.data_ptr(),
+                                             _lib.stream()), "sf_clips_to_flows")
+    return out
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None

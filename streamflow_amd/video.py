@@ -1,0 +1,220 @@
+"""Streaming, batched video inference: uint8 frames in, flow fields out, `clips_per_step` clips per model call.
+
+The counterpart of the reference's `read_video_and_group_predict` (demo.py:502-534) for frames that arrive as bytes -- from a decoder,
+from PNG files (`FrameDir`), or already on the GPU.  Per batch of clips: the uint8 frames the batch needs are uploaded (nothing when
+they are device-resident), ONE sf_frames_to_clips launch normalises, replicate-pads and groups them into [n_clips, T, 3, Hp, Wp], the
+model runs once, ONE sf_clips_to_flows launch crops the kept flow fields into video order.  The host never holds a frame in fp32.
+
+The clip schedule (include/streamflow_hip.h, "video clips") is `demo.group_clips` in closed form; `clip_start`, `pair_clip` and
+`plan_batches` restate it on the host for the batching.  `demo.predict_frames` stays the one-clip-per-call host path.
+"""
+from __future__ import annotations
+
+import glob
+import os
+import struct
+from typing import Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import flow_io
+from .utils import InputPadder
+
+MAX_PAIRS = 8               # SF_VIDEO_MAX_PAIRS: pair pointers one sf_clips_to_flows call takes
+
+
+def clip_count(n: int, T: int) -> int:
+    """Clips of T frames that cover a video of n frames: ceil((n - 1) / (T - 1))."""
+    if T < 2 or n < T:
+        raise ValueError(f"need at least T={T} >= 2 frames, got {n}")
+    return -(-(n - 1) // (T - 1))
+
+
+def clip_start(c: int, n: int, T: int) -> int:
+    """First frame of clip c: clips advance by T - 1 frames, the last one is aligned to the end of the video."""
+    if not 0 <= c < clip_count(n, T):
+        raise ValueError(f"clip {c} of a video with {clip_count(n, T)}")
+    return min(c * (T - 1), n - T)
+
+
+def pair_clip(j: int, n: int, T: int) -> Tuple[int, int]:
+    """(clip, slot inside it) that produces pair j (frames j -> j + 1): the earliest clip that contains the pair."""
+    if not 0 <= j < n - 1:
+        raise ValueError(f"pair {j} of a video with {n - 1}")
+    c = min(j // (T - 1), clip_count(n, T) - 1)
+    return c, j - clip_start(c, n, T)
+
+
+def plan_batches(n: int, T: int, clips_per_step: int) -> List[Tuple[int, int, int, int, int, int]]:
+    """[(first_clip, n_clips, frame_lo, frame_hi, pair_lo, pair_hi)] per model call: the clips first_clip .. first_clip + n_clips - 1
+    read the frames [frame_lo, frame_hi) and produce the pairs [pair_lo, pair_hi) of the video (half-open ranges); the pair ranges
+    of consecutive batches tile 0 .. n - 2 in order.  The last batch may hold fewer clips."""
+    if clips_per_step < 1:
+        raise ValueError(f"clips_per_step must be at least 1, got {clips_per_step}")
+    nc = clip_count(n, T)
+    out = []
+    for first in range(0, nc, clips_per_step):
+        k = min(clips_per_step, nc - first)
+        last = first + k - 1
+        out.append((first, k, clip_start(first, n, T), clip_start(last, n, T) + T, first * (T - 1), min((last + 1) * (T - 1), n - 1)))
+    return out
+
+
+def _png_size(path: str) -> Tuple[int, int]:
+    with open(path, "rb") as f:
+        head = f.read(24)
+    if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        raise IOError(f"{path}: not a PNG file")
+    w, h = struct.unpack(">II", head[16:24])
+    return h, w
+
+
+class FrameDir:
+    """The PNG frames of a directory, sorted by name, as a lazy sequence of uint8 [H, W, 3] arrays: a frame is decoded
+    (flow_io.read_png) when it is indexed and not kept.  Grey frames are replicated to three channels and alpha is dropped, as
+    evaluate._image does.  All frames must have one size: the headers are compared when the object is made, the decoded arrays
+    again when they are read."""
+
+    def __init__(self, path: str, pattern: str = "*.png"):
+        self.paths = sorted(glob.glob(os.path.join(path, pattern)))
+        if not self.paths:
+            raise FileNotFoundError(f"no frames matching {pattern!r} in {path}")
+        self.hw = _png_size(self.paths[0])
+        for p in self.paths[1:]:
+            if _png_size(p) != self.hw:
+                raise ValueError(f"{p}: frame size {_png_size(p)} differs from {self.hw} of {self.paths[0]}")
+
+    def __len__(self) -> int:
+        return len(self.paths)
+
+    def __getitem__(self, i: int) -> np.ndarray:
+        if isinstance(i, slice):
+            raise TypeError("FrameDir is indexed by frame number")
+        img = flow_io.read_png(self.paths[i])
+        if img.ndim == 2 or img.shape[2] == 2:                           # grey, grey + alpha
+            img = np.repeat((img if img.ndim == 2 else img[:, :, 0])[:, :, None], 3, axis=2)
+        img = np.ascontiguousarray(img[:, :, :3]).astype(np.uint8)
+        if img.shape[:2] != self.hw:
+            raise ValueError(f"{self.paths[i]}: frame size {img.shape[:2]} differs from {self.hw}")
+        return img
+
+
+class _Source:
+    """The frames argument of predict_video behind one face: n, (H, W), and `device_frames(lo, hi, dev)` -> (uint8 device tensor,
+    channels_last, number of its first frame).  Everything is checked that can be without touching the GPU or decoding a frame."""
+
+    def __init__(self, frames):
+        self.stack = None                                                # a whole-video tensor / array
+        self.seq = None                                                  # a sequence of [H, W, 3] frames
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8:
+                raise TypeError(f"predict_video: frames must be uint8, got {frames.dtype}")
+            frames = torch.from_numpy(frames)
+        if isinstance(frames, torch.Tensor):
+            if frames.dtype != torch.uint8:
+                raise TypeError(f"predict_video: frames must be uint8, got {frames.dtype} (normalised fp32 frames: demo.predict_frames)")
+            if frames.dim() != 4 or 3 not in (frames.shape[3], frames.shape[1]):
+                raise ValueError(f"predict_video: expected frames [N, H, W, 3] or [N, 3, H, W], got {tuple(frames.shape)}")
+            self.stack = frames
+            self.channels_last = frames.shape[3] == 3
+            self.n = int(frames.shape[0])
+            self.hw = tuple(int(s) for s in (frames.shape[1:3] if self.channels_last else frames.shape[2:]))
+            return
+        if not hasattr(frames, "__len__") or not hasattr(frames, "__getitem__"):
+            raise TypeError(f"predict_video: frames must be a uint8 tensor / array or a sequence of frames, got {type(frames).__name__}")
+        self.seq, self.n, self.channels_last = frames, len(frames), True
+        if isinstance(frames, (list, tuple)):                            # frames already in memory: look at all of them now
+            for i, f in enumerate(frames):
+                self._check(f, i)
+                if tuple(f.shape[:2]) != tuple(frames[0].shape[:2]):
+                    raise ValueError(f"predict_video: frame {i} is {tuple(f.shape[:2])}, frame 0 is {tuple(frames[0].shape[:2])}")
+            self.hw = tuple(int(s) for s in frames[0].shape[:2]) if frames else None
+        else:                                                            # lazy: a `hw` attribute (FrameDir) or the first frame
+            hw = getattr(frames, "hw", None)
+            if hw is None and self.n:
+                first = frames[0]
+                self._check(first, 0)
+                hw = first.shape[:2]
+            self.hw = None if hw is None else (int(hw[0]), int(hw[1]))
+
+    @staticmethod
+    def _check(f, i: int) -> None:
+        dt = getattr(f, "dtype", None)
+        if dt not in (np.uint8, torch.uint8):
+            raise TypeError(f"predict_video: frame {i} must be uint8, got {dt}")
+        if len(f.shape) != 3 or f.shape[2] != 3:
+            raise ValueError(f"predict_video: frame {i} must be [H, W, 3], got {tuple(f.shape)}")
+
+    def device_frames(self, lo: int, hi: int, dev: torch.device):
+        if self.stack is not None:
+            if self.stack.is_cuda:
+                if self.stack.device != dev:
+                    raise RuntimeError(f"predict_video: frames on {self.stack.device}, model on {dev}")
+                return self.stack, self.channels_last, 0
+            return self.stack[lo:hi].to(dev), self.channels_last, lo
+        batch = []
+        for i in range(lo, hi):
+            f = self.seq[i]
+            self._check(f, i)
+            if tuple(f.shape[:2]) != self.hw:
+                raise ValueError(f"predict_video: frame {i} is {tuple(f.shape[:2])}, frame 0 is {self.hw}")
+            batch.append(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)))
+        if all(f.is_cuda for f in batch):
+            return torch.stack(batch), True, lo
+        return torch.stack([f.cpu() for f in batch]).to(dev), True, lo
+
+
+def _model_device(model) -> Optional[torch.device]:
+    try:
+        return next(model.parameters()).device
+    except (AttributeError, StopIteration, TypeError):
+        return None
+
+
+@torch.no_grad()
+def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = None, clips_per_step: int = 8, mode: str = "sintel",
+                  device=None, sink: Optional[Callable[[int, torch.Tensor], None]] = None) -> Optional[torch.Tensor]:
+    """Flow fields of every consecutive frame pair of a video, `clips_per_step` clips per model call.
+
+    frames: a uint8 tensor / array [N, H, W, 3] or [N, 3, H, W] (HWC when both readings fit) on the host or the GPU, or a sequence
+    of uint8 [H, W, 3] frames (`FrameDir`, a list), read batch by batch.  model: `model.forward_normalised(imgs, iters)` when it has
+    one (SKFlow_MF8, StreamFlowT4; `iters=None` = the class's default), else `model(imgs)` as demo.predict_frames calls it; imgs is
+    fp32 [n_clips, T, 3, Hp, Wp] in [-1, 1], the result T - 1 flows [n_clips, 2, Hp, Wp].  mode: InputPadder's.  device: default the
+    frames' GPU, else the model's, else the current one.
+
+    Returns a device tensor [N - 1, 2, H, W]; with `sink`, calls `sink(first_pair, flows[k, 2, H, W])` per batch in video order,
+    keeps nothing and returns None (long videos, writing to disk).  Nothing here synchronises with the host."""
+    from . import ops
+    src = _Source(frames)
+    if T < 2 or T - 1 > MAX_PAIRS:
+        raise ValueError(f"predict_video: T = {T} (2 .. {MAX_PAIRS + 1}: at most {MAX_PAIRS} pairs per clip)")
+    if src.n < T:
+        raise ValueError(f"predict_video: need at least T={T} frames, got {src.n}")
+    batches = plan_batches(src.n, T, int(clips_per_step))
+    if device is None:
+        device = src.stack.device if src.stack is not None and src.stack.is_cuda else _model_device(model)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError(f"predict_video runs on the GPU (device {dev}, GPU available: {torch.cuda.is_available()}); there is no CPU "
+                           "fallback -- demo.predict_frames is the host-side path")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    H, W = src.hw
+    pad = InputPadder((H, W), mode=mode)._pad
+    call = (lambda x: model.forward_normalised(x, iters)) if hasattr(model, "forward_normalised") else model
+    out = None if sink is not None else torch.empty(src.n - 1, 2, H, W, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for first, k, f_lo, f_hi, p_lo, p_hi in batches:
+            buf, channels_last, frame0 = src.device_frames(f_lo, f_hi, dev)
+            imgs = ops.frames_to_clips(buf, src.n, T, first, k, pad, frame0=frame0, channels_last=channels_last)
+            flows = list(call(imgs))
+            if len(flows) != T - 1:
+                raise RuntimeError(f"predict_video: the model returned {len(flows)} flows for clips of T = {T}")
+            got = ops.clips_to_flows(flows, src.n, T, first, p_lo, p_hi - p_lo, (H, W), pad,
+                                     out=None if out is None else out[p_lo:p_hi])
+            if sink is not None:
+                sink(p_lo, got)
+    return out
