@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 125
+#define SF_VERSION 126
 
 enum {
     SF_OK = 0,
@@ -631,6 +631,52 @@ enum {
 #define SF_SCORE_WS_BYTES (1024 * SF_SCORE_LEN * 8)
 int sf_flow_score(const float* pred, int64_t pred_ch_stride, int64_t pred_row_stride, const float* gt, int gt_h, int gt_w,
                   int step, int h, int w, double* acc, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- Sintel / KITTI scoring, a batch of fields per call (evaluate_mf.py:106-142, :468-503, :549-592) --------------------------
+ * Scores n_fields (1 .. SF_SCORE_BATCH_MAX) predicted fields of one size h x w, field i against its own ground truth, and ADDS
+ * the result of field i into row i of acc[n_fields][SF_EVAL_LEN] (fp64, on the device).  `f` is a HOST table that travels in the
+ * kernel arguments (entries at and above n_fields are not looked at); nothing is uploaded.
+ *   pred[i]: fp32 planes [2][h][w]: u at pred[i][y * pred_row_stride + x], v at the same + pred_ch_stride (strides in floats,
+ *            shared by all fields: windows of the model's padded outputs, slices of one tensor).
+ *   gt[i]:   the ground truth as its decoder left it, dense:
+ *            SF_GT_FLO32    fp32 [h][w][2] = (u, v) (a .flo file); valid = !isnan(gu + gv);
+ *            SF_GT_KITTI16  uint16 [h][w][3] = (u, v, valid) samples of a KITTI flow_occ PNG, decoded here:
+ *                           gu = ((float)s0 - 32768) / 64, gv likewise (exact in fp32), valid = s2 != 0.
+ *   mask[i]: NULL for every field, or for every field uint8 [h][w], the bytes of a Sintel occlusions PNG: a pixel is occluded when
+ *            its byte is 255, non-occluded otherwise (the reference's astype(uint8) // 255 as bool).
+ *   ws:      scratch of sf_flow_score_batch_ws_bytes(n_fields, h, w) bytes (per-block partials); it is not read by later calls.
+ * Per pixel, fp32 with every operation rounded on its own (no contraction; correctly rounded square root and division):
+ *   e = sqrt((pu - gu)(pu - gu) + (pv - gv)(pv - gv)),  mag = sqrt(gu gu + gv gv),
+ *   outlier = valid && e > 3 && e / mag > 0.05   (IEEE for mag = 0: e / 0 = inf is an outlier, 0 / 0 = NaN is not).
+ * Entries of a row (counts are exact in fp64 below 2^53; NaN compares false):
+ *   PIXELS         pixels                       SUM_EPE        sum of e (fp64; NaN if any e is NaN)
+ *   LT1 / LT3 / LT5  pixels with e < 1 / 3 / 5
+ *   VALID          valid pixels                 SUM_EPE_VALID  sum of e over valid pixels          OUTLIER  outlier pixels
+ *   OCC            occluded pixels              SUM_EPE_OCC    sum of e over them      (these four stay as they are
+ *   NOC            non-occluded pixels          SUM_EPE_NOC    sum of e over them       without masks)
+ * Vector loads (16 bytes of a prediction plane, 16 / 8 of fp32 and 8 / 4 of 16-bit ground truth, 4 mask bytes) where pointers,
+ * strides and w allow them, element loads otherwise.  Deterministic: per-block partials summed in a fixed order by a second kernel
+ * (one block per field), no atomics, a grid that depends on (n_fields, h, w) alone; repeated calls give bitwise equal accumulators.
+ * Two kernels on `stream`, no host synchronisation.
+ * SF_ERR_BAD_ARG before any launch for: a null f, acc or ws; n_fields outside 1 .. SF_SCORE_BATCH_MAX; an unknown gt_kind;
+ * h, w <= 0 or h * w >= 2^30; pred_row_stride < w or pred_ch_stride == 0; ws_bytes too small; acc or ws not 8-byte aligned; a null
+ * pred[i] or gt[i]; a pred[i] or gt[i] not aligned to its element size (4; 4 or 2); masks for some fields only.
+ * sf_flow_score_batch_ws_bytes returns SF_ERR_BAD_ARG for n_fields, h, w outside the limits above. */
+#define SF_SCORE_BATCH_MAX 32
+enum { SF_GT_FLO32 = 0, SF_GT_KITTI16 = 1 };
+enum {
+    SF_EVAL_PIXELS = 0, SF_EVAL_SUM_EPE = 1, SF_EVAL_LT1 = 2, SF_EVAL_LT3 = 3, SF_EVAL_LT5 = 4, SF_EVAL_VALID = 5,
+    SF_EVAL_SUM_EPE_VALID = 6, SF_EVAL_OUTLIER = 7, SF_EVAL_OCC = 8, SF_EVAL_SUM_EPE_OCC = 9, SF_EVAL_NOC = 10,
+    SF_EVAL_SUM_EPE_NOC = 11, SF_EVAL_LEN = 12
+};
+typedef struct SfScoreFields {
+    const float* pred[SF_SCORE_BATCH_MAX];
+    const void* gt[SF_SCORE_BATCH_MAX];
+    const uint8_t* mask[SF_SCORE_BATCH_MAX];
+} SfScoreFields;
+int64_t sf_flow_score_batch_ws_bytes(int n_fields, int h, int w);
+int sf_flow_score_batch(const SfScoreFields* f, int n_fields, int64_t pred_ch_stride, int64_t pred_row_stride, int gt_kind, int h,
+                        int w, double* acc, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- video clips: uint8 frames -> clip batches, per-pair outputs -> flows in video order (demo.py:502-534) ---------------------
  * The clip schedule of the reference's read_video_and_group_predict, in closed form (streamflow_amd.demo.group_clips states the

@@ -100,6 +100,10 @@ class SfPairPtrs(C.Structure):
     _fields_ = [("p", _vp * 8)]
 
 
+class SfScoreFields(C.Structure):
+    _fields_ = [("pred", _vp * 32), ("gt", _vp * 32), ("mask", _vp * 32)]
+
+
 class SfTilePlan(C.Structure):
     _fields_ = [
         ("n_seq", C.c_int32), ("n_distinct", C.c_int32), ("tile_h", C.c_int32), ("tile_w", C.c_int32),
@@ -176,6 +180,8 @@ SIGNATURES = {
     "sf_tile_blend": (_i, [_vp, _vp, _vp, C.POINTER(SfTilePlan), _i, _i, _vp]),
     "sf_flow_to_image": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
     "sf_flow_score": (_i, [_vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "sf_flow_score_batch_ws_bytes": (_i64, [_i, _i, _i]),
+    "sf_flow_score_batch": (_i, [C.POINTER(SfScoreFields), _i, _i64, _i64, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "sf_frames_to_clips": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_clips_to_flows": (_i, [C.POINTER(SfPairPtrs), _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
@@ -203,7 +209,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 125:
+    if lib.sf_version() < 126:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

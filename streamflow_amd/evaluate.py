@@ -18,8 +18,21 @@
   ground truth subsampled [::2, ::2]); device flows are scored where they are by the sf_flow_score kernel (ops.flow_score),
   host flows by streamflow_amd.scoring.score_host with the same arithmetic.
 
+* ``validate_sintel_occ_mf(model, iters, root, tqdm_miniters, nframes)`` -- evaluate_mf.py:549-592: the passes albedo, clean and
+  final with the EPE also taken over occluded and non-occluded pixels apart (``root/training/occlusions/<scene>/frame_XXXX.png``,
+  8-bit gray, occluded where 255).
+* ``clips_per_step=k > 1`` (sintel_report, validate_sintel_mf, validate_sintel_occ_mf, validate_kitti_mf): k clips per model call
+  and nothing but the accumulator leaves the GPU -- a Sintel scene goes through video.predict_video as uint8 frames (every frame
+  decoded and uploaded once) and each batch's flows are scored where they are, against the .flo arrays as read, by
+  ops.flow_score_batch (the sf_flow_score_batch kernel); KITTI sequences of one frame size are collected k at a time, each clip
+  built by ops.frames_to_clips, one model call, the last pairs scored against the 16-bit PNG samples in one launch.  The
+  default ``clips_per_step=1`` is the reference's loop, one clip per call, scored on the host.  ``python -m
+  streamflow_amd.evaluate --dataset ..`` is the reference's ``evaluate_mf.py --dataset`` switch.
+
 ``model`` is anything with the reference's test-mode call ``model(images: list of [1,3,H,W] in 0..255, iters=.., test_mode=True)
--> list of nframes - 1 flows [1,2,H,W]`` (streamflow_amd.SKFlow_MF8, or the CPU oracle wrapped the same way in the tests).
+-> list of nframes - 1 flows [1,2,H,W]`` (streamflow_amd.SKFlow_MF8, or the CPU oracle wrapped the same way in the tests); with
+``clips_per_step > 1`` it is called as video.predict_video calls it (``model.forward_normalised(clips, iters)``, else
+``model(clips)``, clips fp32 [k, T, 3, Hp, Wp] in [-1, 1]) and must live on a GPU: there is no host fallback.
 Files are read with this package's own codecs (flow_io.py: PNG, .flo, KITTI 16-bit PNG; flo5.py: Spring's .flo5).  Host-side
 plumbing: the kernels launched here are the tile blend of the tiled validators (ops.tile_blend) for models without
 ``forward_tiled`` and the Spring scoring (ops.flow_score).
@@ -74,9 +87,14 @@ def _device_of(model) -> torch.device:
 
 @torch.no_grad()
 def sintel_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", nframes: int = 3,
-                  dstypes: Sequence[str] = ("clean", "final"), device: Optional[torch.device] = None) -> Dict[str, Dict[str, float]]:
-    """Per render pass: {'epe', '1px', '3px', '5px', 'pairs'} over every scored pair of every scene."""
+                  dstypes: Sequence[str] = ("clean", "final"), device: Optional[torch.device] = None, clips_per_step: int = 1,
+                  occ: bool = False) -> Dict[str, Dict[str, float]]:
+    """Per render pass: {'epe', '1px', '3px', '5px', 'pairs'} over every scored pair of every scene.  clips_per_step > 1: that many
+    clips per model call, scored on the GPU (_sintel_report_scored; adds 'pixels'); occ: also 'epe_occ', 'epe_noc', 'occ_pixels'
+    from the scenes' occlusion maps."""
     dev = device or _device_of(model)
+    if int(clips_per_step) != 1 or occ:
+        return _sintel_report_scored(model, iters, root, nframes, dstypes, dev, int(clips_per_step), bool(occ))
     report = {}
     for dstype in dstypes:
         image_root = os.path.join(root, "training", dstype)
@@ -107,15 +125,135 @@ def sintel_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
 
 @torch.no_grad()
 def validate_sintel_mf(model: Callable, iters: int = 6, root: str = "/data/Sintel", tqdm_miniters: int = 1, nframes: int = 3,
-                       device: Optional[torch.device] = None) -> Dict[str, float]:
+                       device: Optional[torch.device] = None, clips_per_step: int = 1) -> Dict[str, float]:
     """The reference's return value: {'clean': mean EPE, 'final': mean EPE}  (evaluate_mf.py:468-503)."""
-    return {k: v["epe"] for k, v in sintel_report(model, iters, root, nframes, device=device).items()}
+    return {k: v["epe"] for k, v in sintel_report(model, iters, root, nframes, device=device,
+                                                  clips_per_step=clips_per_step).items()}
+
+
+@torch.no_grad()
+def validate_sintel_occ_mf(model: Callable, iters: int = 6, root: str = "/data/Sintel", tqdm_miniters: int = 1, nframes: int = 3,
+                           clips_per_step: int = 1, device: Optional[torch.device] = None) -> Dict[str, float]:
+    """The reference's validate_sintel_occ_mf (evaluate_mf.py:549-592): the passes albedo, clean and final, per pass the line of
+    validate_sintel_mf and "Occ epe: .., Noc epe: .."; returns {pass: mean EPE}.  `tqdm_miniters` is accepted and ignored."""
+    if hasattr(model, "eval"):
+        model.eval()
+    rep = sintel_report(model, iters, root, nframes, dstypes=("albedo", "clean", "final"), device=device,
+                        clips_per_step=clips_per_step, occ=True)
+    return {k: v["epe"] for k, v in rep.items()}
+
+
+def _frame_u8(path: str) -> np.ndarray:
+    """A PNG frame as uint8 [H, W, 3] (grey replicated, alpha dropped: what _image makes of it, before the conversion to float)."""
+    img = flow_io.read_png(path)
+    if img.ndim == 2:
+        img = np.repeat(img[:, :, None], 3, axis=2)
+    return np.ascontiguousarray(img[:, :, :3]).astype(np.uint8)
+
+
+def _occlusion(path: str, hw: Tuple[int, int]) -> np.ndarray:
+    m = flow_io.read_png(path)
+    if m.ndim != 2 or m.dtype != np.uint8 or tuple(m.shape) != tuple(hw):
+        raise RuntimeError(f"{path}: an occlusion map is an 8-bit gray PNG of {hw[0]} x {hw[1]}, got {m.dtype} {m.shape}")
+    return np.ascontiguousarray(m)
+
+
+def _need_gpu(what: str, dev: torch.device) -> torch.device:
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError(f"{what}: clips_per_step > 1 runs on the GPU (device {dev}, GPU available: {torch.cuda.is_available()}); "
+                           "there is no CPU fallback -- clips_per_step=1 is the host-side path")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _sintel_report_scored(model: Callable, iters: int, root: str, nframes: int, dstypes: Sequence[str], dev: torch.device,
+                          clips_per_step: int, occ: bool) -> Dict[str, Dict[str, float]]:
+    """sintel_report through the EVAL accumulator (scoring.py): one row per scored pair.  clips_per_step > 1: per scene, the uint8
+    frames (each decoded once) go through video.predict_video and every batch's flows are scored as they arrive (its `sink`), so
+    neither a flow nor a whole scene's flows leave the GPU or stay on it.  clips_per_step == 1: the per-clip loop of sintel_report,
+    device flows scored by ops.flow_score_batch, host flows (a CPU model) by scoring.score_host_fields with the same arithmetic.
+    The device rows are copied to the host once, at the end of the report."""
+    from . import ops, scoring, video
+    if clips_per_step < 1:
+        raise ValueError(f"clips_per_step must be at least 1, got {clips_per_step}")
+    if clips_per_step > 1:
+        dev = _need_gpu("sintel_report", dev)
+    rows = {d: [] for d in dstypes}                                      # per pass: [k, EVAL_LEN] arrays (host) / tensors (device)
+    for dstype in dstypes:
+        image_root = os.path.join(root, "training", dstype)
+        flow_root = os.path.join(root, "training", "flow")
+        occ_root = os.path.join(root, "training", "occlusions")
+        for scene in _scenes(image_root):
+            imgs = sorted(glob.glob(os.path.join(image_root, scene, "*.png")))
+            flos = sorted(glob.glob(os.path.join(flow_root, scene, "*.flo")))
+            if len(flos) != len(imgs) - 1:
+                raise RuntimeError(f"{scene}: {len(imgs)} frames need {len(imgs) - 1} .flo files, found {len(flos)}")
+            occs = sorted(glob.glob(os.path.join(occ_root, scene, "*.png"))) if occ else None
+            if occ and len(occs) != len(flos):
+                raise RuntimeError(f"{scene}: {len(flos)} .flo files need as many occlusion maps under {occ_root}, found {len(occs)}")
+
+            def truth(pairs: Sequence[int]):
+                gts = [flow_io.read_flo(flos[j]) for j in pairs]
+                return gts, ([_occlusion(occs[j], gts[0].shape[:2]) for j in pairs] if occ else None)
+
+            if clips_per_step > 1:
+                acc = torch.zeros(len(flos), scoring.EVAL_LEN, dtype=torch.float64, device=dev)
+
+                def score(first_pair: int, flows: torch.Tensor, acc=acc, truth=truth) -> None:
+                    gts, masks = truth(range(first_pair, first_pair + flows.shape[0]))
+                    g = torch.from_numpy(np.stack(gts)).to(flows.device)
+                    m = None if masks is None else list(torch.from_numpy(np.stack(masks)).to(flows.device))
+                    ops.flow_score_batch(list(flows), list(g), acc[first_pair:first_pair + flows.shape[0]], "flo", m)
+
+                video.predict_video(model, [_frame_u8(p) for p in imgs], T=nframes, iters=iters, clips_per_step=clips_per_step,
+                                    mode="sintel", device=dev, sink=score)
+                rows[dstype].append(acc)
+                continue
+            for first, ids in sintel_clip_schedule(len(imgs), nframes):
+                images = [_image(p)[None].to(dev) for p in imgs[first:first + nframes]]
+                padder = InputPadder(images[0].shape)
+                flows = model(padder.pad_list(images), iters=iters, test_mode=True)
+                keep = [i for i in range(nframes - 1) if ids[i] != -1]
+                preds = [padder.unpad(flows[i][0]).float() for i in keep]
+                gts, masks = truth([first + i for i in keep])
+                if preds[0].is_cuda:
+                    d = preds[0].device
+                    acc = torch.zeros(len(keep), scoring.EVAL_LEN, dtype=torch.float64, device=d)
+                    ops.flow_score_batch(preds, [torch.from_numpy(g).to(d) for g in gts], acc, "flo",
+                                         None if masks is None else [torch.from_numpy(m).to(d) for m in masks])
+                else:
+                    acc = np.zeros((len(keep), scoring.EVAL_LEN), np.float64)
+                    for j, pred in enumerate(preds):
+                        scoring.score_host_fields(pred.numpy(), gts[j], acc[j], "flo", None if masks is None else masks[j])
+                rows[dstype].append(acc)
+    # one copy to the host for the whole report
+    on_dev = [(d, i) for d in dstypes for i, r in enumerate(rows[d]) if isinstance(r, torch.Tensor)]
+    if on_dev:
+        host = torch.cat([rows[d][i].to(rows[on_dev[0][0]][on_dev[0][1]].device) for d, i in on_dev]).cpu().numpy()
+        at = 0
+        for d, i in on_dev:
+            k = rows[d][i].shape[0]
+            rows[d][i] = host[at:at + k]
+            at += k
+    report = {}
+    for dstype in dstypes:
+        if not rows[dstype]:
+            raise RuntimeError(f"sintel_report: no pairs scored under {os.path.join(root, 'training', dstype)}")
+        m = scoring.sintel_from(np.concatenate(rows[dstype]))
+        print("Validation (%s) EPE: %f, 1px: %f, 3px: %f, 5px: %f" % (dstype, m["epe"], m["1px"], m["3px"], m["5px"]))
+        if occ:
+            print("Occ epe: %f, Noc epe: %f" % (m["epe_occ"], m["epe_noc"]))
+        else:
+            for k in ("epe_occ", "epe_noc", "occ_pixels"):
+                del m[k]
+        report[dstype] = m
+    return report
 
 
 @torch.no_grad()
 def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str] = None, nframes: int = 3,
-                      device: Optional[torch.device] = None) -> Dict[str, float]:
-    """{'kitti_epe', 'kitti_f1'} over the sequences present under multi_root/training (the reference walks 000000 .. 000199)."""
+                      device: Optional[torch.device] = None, clips_per_step: int = 1) -> Dict[str, float]:
+    """{'kitti_epe', 'kitti_f1'} over the sequences present under multi_root/training (the reference walks 000000 .. 000199).
+    clips_per_step > 1: up to that many sequences of one frame size per model call, scored on the GPU (_kitti_batched)."""
     if multi_root is None:
         raise ValueError("validate_kitti_mf: multi_root (the multi-frame KITTI-2015 tree) is required")
     dev = device or _device_of(model)
@@ -124,6 +262,8 @@ def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str]
     seqs = sorted(os.path.basename(p)[:6] for p in glob.glob(os.path.join(flow_root, "??????_10.png")))
     if not seqs:
         raise RuntimeError(f"no ground truth under {flow_root}")
+    if int(clips_per_step) != 1:
+        return _kitti_batched(model, iters, image_root, flow_root, seqs, nframes, dev, int(clips_per_step))
     out_list, epe_list = [], []
     for seq in seqs:
         images = [_image(os.path.join(image_root, "%s_%02d.png" % (seq, i)))[None].to(dev) for i in range(12 - nframes, 12)]
@@ -141,6 +281,61 @@ def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str]
         out_list.append(out[val].numpy())
     epe = float(np.mean(np.array(epe_list)))
     f1 = float(100 * np.mean(np.concatenate(out_list)))
+    print("Validation KITTI: %f, %f" % (epe, f1))
+    return {"kitti_epe": epe, "kitti_f1": f1}
+
+
+def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str, seqs: Sequence[str], nframes: int,
+                   dev: torch.device, clips_per_step: int) -> Dict[str, float]:
+    """validate_kitti_mf, `clips_per_step` sequences per model call: consecutive sequences whose frames have one size (KITTI has
+    five widths) are collected, each one's uint8 frames become a clip by ops.frames_to_clips (a video of n = T frames, 'kitti'
+    padding), the clips run as one batch, and the last pair of every clip is scored in one ops.flow_score_batch call against the
+    16-bit PNG samples as read (decoded in the kernel).  A size change and the end of the list flush the batch.  One accumulator
+    row per sequence; scoring.kitti_from forms the reference's mean of per-image means and the F1-all rate."""
+    from . import ops, scoring
+    if clips_per_step < 1:
+        raise ValueError(f"clips_per_step must be at least 1, got {clips_per_step}")
+    dev = _need_gpu("validate_kitti_mf", dev)
+    T = int(nframes)
+    call = (lambda x: model.forward_normalised(x, iters)) if hasattr(model, "forward_normalised") else model
+    rows, pending = [], []                                              # device rows [k, EVAL_LEN]; (frames [T, H, W, 3], samples)
+
+    def flush() -> None:
+        if not pending:
+            return
+        k = len(pending)
+        H, W = pending[0][0].shape[1:3]
+        pad = InputPadder((H, W), mode="kitti")._pad                     # [left, right, top, bottom]
+        frames = torch.from_numpy(np.stack([f for f, _ in pending])).to(dev)
+        clips = torch.empty(k, T, 3, H + pad[2] + pad[3], W + pad[0] + pad[1], dtype=torch.float32, device=dev)
+        for i in range(k):
+            ops.frames_to_clips(frames[i], T, T, 0, 1, pad, channels_last=True, out=clips[i:i + 1])
+        flows = list(call(clips))
+        if len(flows) != T - 1:
+            raise RuntimeError(f"validate_kitti_mf: the model returned {len(flows)} flows for clips of T = {T}")
+        last = flows[T - 2].float()                                      # only the last pair (frames 10 -> 11) has ground truth
+        preds = [last[i][:, pad[2]:pad[2] + H, pad[0]:pad[0] + W] for i in range(k)]
+        # (the 16-bit samples travel as int16: the same bits, a dtype every torch build can copy to the device)
+        gts = torch.from_numpy(np.stack([g for _, g in pending]).view(np.int16)).to(dev)
+        acc = torch.zeros(k, scoring.EVAL_LEN, dtype=torch.float64, device=dev)
+        ops.flow_score_batch(preds, list(gts), acc, "kitti")
+        rows.append(acc)
+        pending.clear()
+
+    with torch.cuda.device(dev):
+        for seq in seqs:
+            frames = np.stack([_frame_u8(os.path.join(image_root, "%s_%02d.png" % (seq, i))) for i in range(12 - T, 12)])
+            path = os.path.join(flow_root, seq + "_10.png")
+            smp = flow_io.read_png(path)
+            if smp.ndim != 3 or smp.shape[2] < 3 or smp.dtype != np.uint16:
+                raise IOError(f"{path}: KITTI flow needs a 16-bit RGB PNG, got {smp.dtype} {smp.shape}")
+            if smp.shape[:2] != frames.shape[1:3]:
+                raise RuntimeError(f"{path}: ground truth {smp.shape[:2]} for frames {frames.shape[1:3]}")
+            if pending and (len(pending) == clips_per_step or pending[0][0].shape != frames.shape):
+                flush()
+            pending.append((frames, np.ascontiguousarray(smp[:, :, :3])))
+        flush()
+        epe, f1 = scoring.kitti_from(torch.cat(rows))
     print("Validation KITTI: %f, %f" % (epe, f1))
     return {"kitti_epe": epe, "kitti_f1": f1}
 
@@ -319,3 +514,54 @@ def validate_kitti_tile(model: Callable, iters: int = 6, root: Optional[str] = N
 
     epe, f1 = _kitti_scores(pairs())
     return {"kitti-epe": epe, "kitti-f1": f1}
+
+
+# ---- command line (the reference's evaluate_mf.py --dataset switch) -----------------------------------------------------------
+def load_model(ckpt: str, T: int = 4, preset: Optional[str] = None, device: Optional[torch.device] = None):
+    """SKFlow_MF8 for clips of T frames with the checkpoint loaded strictly, as StreamFlowT4 loads it ({'model': state_dict} or a
+    bare dict, keys optionally prefixed 'module.'), on `device` (default: the current GPU) in eval mode."""
+    from .model import SKFlow_MF8, default_args
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("evaluate: the model runs on the GPU; there is no CPU fallback")
+        device = torch.device("cuda", torch.cuda.current_device())
+    obj = torch.load(ckpt, map_location="cpu")
+    sd = obj["model"] if isinstance(obj, dict) and "model" in obj else obj
+    sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+    model = SKFlow_MF8(default_args(T=T, preset=preset))
+    model.load_state_dict(sd, strict=True)
+    for p in model.parameters():
+        p.requires_grad = False
+    return model.to(device).eval()
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m streamflow_amd.evaluate",
+                                 description="Validate a StreamFlow checkpoint on a dataset tree (the reference's evaluate_mf.py)")
+    ap.add_argument("--dataset", required=True, choices=("sintel", "sintel_occ", "kitti", "kitti_tile", "spring"))
+    ap.add_argument("--ckpt", required=True, help="StreamFlow checkpoint")
+    ap.add_argument("--root", required=True, help="dataset tree (Sintel, multi-frame KITTI-2015 or Spring layout)")
+    ap.add_argument("--T", type=int, default=4, help="frames per clip")
+    ap.add_argument("--iters", type=int, default=6)
+    ap.add_argument("--clips-per-step", type=int, default=8,
+                    help="clips per model call (sintel, sintel_occ, kitti; 1 = the reference's per-clip loop scored on the host)")
+    ap.add_argument("--preset", default=None, help="arithmetic preset (streamflow_amd.presets); default: fp32_class")
+    a = ap.parse_args(argv)
+    model = load_model(a.ckpt, T=a.T, preset=a.preset)
+    if a.dataset == "sintel":
+        res = validate_sintel_mf(model, iters=a.iters, root=a.root, nframes=a.T, clips_per_step=a.clips_per_step)
+    elif a.dataset == "sintel_occ":
+        res = validate_sintel_occ_mf(model, iters=a.iters, root=a.root, nframes=a.T, clips_per_step=a.clips_per_step)
+    elif a.dataset == "kitti":
+        res = validate_kitti_mf(model, iters=a.iters, multi_root=a.root, nframes=a.T, clips_per_step=a.clips_per_step)
+    elif a.dataset == "kitti_tile":
+        res = validate_kitti_mf_tile(model, iters=a.iters, multi_root=a.root, nframes=a.T)
+    else:
+        res = {"spring": validate_spring_mf(model, iters=a.iters, root=a.root, nframes=a.T)}
+    print(" ".join("%s: %f" % (k, v) for k, v in res.items()))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -1277,6 +1277,73 @@ def flow_score(pred: torch.Tensor, gt: torch.Tensor, acc: torch.Tensor, step: in
                                          _lib.stream()), "sf_flow_score")
 
 
+@on_tensor_device
+def flow_score_batch(preds: Sequence[torch.Tensor], gts: Sequence[torch.Tensor], acc: torch.Tensor, kind: str = "flo",
+                     masks: Optional[Sequence[torch.Tensor]] = None) -> None:
+    """Add the Sintel / KITTI scores of field i to row i of `acc` (sf_flow_score_batch; reference evaluate_mf.py:106-142, :468-503,
+    :549-592), up to 32 fields per call (two launches), longer sequences in several calls.  preds: fp32 [2, h, w] views on one GPU
+    whose rows are contiguous and whose strides agree (padder.unpad(flow[k]) of the model's padded outputs, slices of
+    predict_video's result: no copy); gts: per field, contiguous, as decoded -- kind "flo": fp32 [h, w, 2] (flow_io.read_flo), kind
+    "kitti": the 16-bit samples [h, w, 3] of a flow_occ PNG (flow_io.read_png) as uint16 or, the same bits, int16; masks: None or
+    per field contiguous uint8 [h, w], occluded where 255; acc: contiguous float64 [len(preds), scoring.EVAL_LEN].  Enqueued on
+    the current stream, no synchronisation; scoring.sintel_from / kitti_from form the reports."""
+    from . import scoring
+    preds, gts = list(preds), list(gts)
+    masks = None if masks is None else list(masks)
+    n = len(preds)
+    if kind not in scoring.GT_KINDS:
+        raise ValueError(f"flow_score_batch: kind {kind!r} ('flo' or 'kitti')")
+    if n == 0 or len(gts) != n or (masks is not None and len(masks) != n):
+        raise ValueError(f"flow_score_batch: {n} predictions, {len(gts)} ground truths"
+                         + ("" if masks is None else f", {len(masks)} masks") + " (equal and at least one)")
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda:
+        raise RuntimeError("flow_score_batch: acc must be on the GPU; host flows are scored by streamflow_amd.scoring.score_host_fields")
+    dev, p0 = acc.device, preds[0]
+    if acc.dtype != torch.float64 or tuple(acc.shape) != (n, scoring.EVAL_LEN) or not acc.is_contiguous():
+        raise RuntimeError(f"flow_score_batch: acc must be contiguous float64 [{n}, {scoring.EVAL_LEN}] "
+                           f"(got {acc.dtype} {tuple(acc.shape)})")
+    h, w = (int(p0.shape[1]), int(p0.shape[2])) if p0.dim() == 3 else (0, 0)
+    gt_shape = (h, w, 2) if kind == "flo" else (h, w, 3)
+    gt_dtypes = (torch.float32,) if kind == "flo" else tuple(d for d in (getattr(torch, "uint16", None), torch.int16) if d is not None)
+    for i, p in enumerate(preds):
+        if not p.is_cuda or p.device != dev:
+            raise RuntimeError(f"flow_score_batch: prediction {i} on {p.device}, acc on {dev}; there is no CPU fallback")
+        if p.dtype != torch.float32 or p.dim() != 3 or p.shape[0] != 2 or p.numel() == 0 or p.stride(2) != 1:
+            raise RuntimeError(f"flow_score_batch: prediction {i} must be fp32 [2, h, w] with contiguous rows (got {p.dtype} "
+                               f"{tuple(p.shape)}, strides {p.stride()})")
+        if p.shape != p0.shape or p.stride() != p0.stride():
+            raise RuntimeError(f"flow_score_batch: prediction {i} is {tuple(p.shape)} with strides {p.stride()}, prediction 0 "
+                               f"{tuple(p0.shape)} with {p0.stride()}")
+        g = gts[i]
+        if not g.is_cuda or g.device != dev:
+            raise RuntimeError(f"flow_score_batch: ground truth {i} on {g.device}, acc on {dev}; there is no CPU fallback")
+        if g.dtype not in gt_dtypes or tuple(g.shape) != gt_shape or not g.is_contiguous():
+            raise RuntimeError(f"flow_score_batch: ground truth {i} of kind {kind!r} must be contiguous {gt_dtypes[0]} "
+                               f"{list(gt_shape)} (got {g.dtype} {tuple(g.shape)}, contiguous={g.is_contiguous()})")
+        if masks is not None:
+            m = masks[i]
+            if not m.is_cuda or m.device != dev:
+                raise RuntimeError(f"flow_score_batch: mask {i} on {m.device}, acc on {dev}; there is no CPU fallback")
+            if m.dtype != torch.uint8 or tuple(m.shape) != (h, w) or not m.is_contiguous():
+                raise RuntimeError(f"flow_score_batch: mask {i} must be contiguous uint8 [{h}, {w}] (got {m.dtype} {tuple(m.shape)})")
+    lib = _lib.load()
+    step = scoring.SCORE_BATCH_MAX
+    ws = torch.empty(int(lib.sf_flow_score_batch_ws_bytes(min(n, step), h, w)), dtype=torch.uint8, device=dev)
+    for lo in range(0, n, step):
+        k = min(step, n - lo)
+        tab = _lib.SfScoreFields()
+        for i in range(k):
+            tab.pred[i], tab.gt[i] = preds[lo + i].data_ptr(), gts[lo + i].data_ptr()
+            if masks is not None:
+                tab.mask[i] = masks[lo + i].data_ptr()
+        need = int(lib.sf_flow_score_batch_ws_bytes(k, h, w))
+        if need > ws.numel():                                           # (a shorter last call may give each field more blocks)
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.sf_flow_score_batch(C.byref(tab), k, p0.stride(0), p0.stride(1), scoring.GT_KINDS[kind], h, w,
+                                           acc[lo:lo + k].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream()),
+                   "sf_flow_score_batch")
+
+
 _NORM_LUT = {}            # device -> the normalisation table of frames_to_clips
 
 
