@@ -347,7 +347,11 @@ int sf_gma_stored_aggregate(void* ws, int64_t ws_bytes, const void* pbuf, int64_
  * mode 1 (an ffn1 pair, M2 == K1): x1 = gelu(x + y); x2 = gelu(x1 + dw_w * x1 + dw_b)  (update.py:31-32: residual, then the
  *   depthwise 1x1 layer of conv_list); C16 = x2 as fp16 ROWS [M2][ldc16].  The residual is the fp16 operand itself.
  * Shapes built: the SK blocks of the update block (C = 128 / 256 / 324) and the flow head (384 / 256 / 128 -> 2 (T - 1) rows); see the
- * dispatch table in csrc/ffn_pair.hip. */
+ * dispatch table in csrc/ffn_pair.hip.
+ * N: any pixel count > 0 -- no multiple of the tile (64 or 128 pixels) or of 4 is required: a lane past N neither loads nor stores.
+ * Every ld* >= N; columns [N, ld), the gaps between images and groups and the rows >= K1 of X's last octet are never part of a
+ * result (the latter must be finite) and nothing outside [image][row < M2][pixel < N] is written, except the rows >= M2 of C16's
+ * last octet when c16_partial = 0 (they receive 0). */
 typedef struct SfFfnPair {
     const void* X; int64_t strideX; int64_t ldx;
     const void* wstream; int64_t wstream_bytes;
@@ -380,7 +384,10 @@ int sf_ffn_pair_frags(int K1, int M2, int pm1, int pm2);
  *   Weights pre-scaled by a power of two per layer (alpha* = 1 / scale, bias* carry the scale).
  * Y (fp32 planes [M2][ldy], optional) and / or Y16 (fp16 k-octet planes, optional; y16_partial = 1: rows >= M2 of the last octet
  * are left alone).  gelu_out: y = gelu(...).  Built for (C, M2) = (256, 192), (256, 126), (384, 6), (128, 64), H % 32 == 0, H <= 576,
- * pm = 1 / 2; anything else: SF_ERR_BAD_ARG (the caller keeps the three launches). */
+ * pm = 1 / 2; anything else: SF_ERR_BAD_ARG (the caller keeps the three launches).
+ * N: any pixel count > 0 (no multiple of the 128-pixel tile or of 4); X needs no alignment beyond its element (2 bytes), ldx / ldy /
+ * ldy16 >= N; nothing outside [image][row < M2][pixel < N] is written, except the rows >= M2 of Y16's last octet when y16_partial = 0
+ * (they receive 0). */
 typedef struct SfSkTail {
     const void* X; int64_t strideX; int64_t ldx;
     const void* wstream; int64_t wstream_bytes;

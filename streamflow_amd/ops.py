@@ -474,11 +474,13 @@ class PackedTail(_PackedStream):
 
 def sk_tail_ok(tail: Optional[PackedTail], X: Planes, Y: Planes, cx: Optional["Ctx"] = None) -> bool:
     """Does sf_sk_tail run this block's back half?  fp16-activation arithmetic, x3 as fp16 ROWS, one product count for the three
-    layers, a built shape, k-octet and / or fp32 outputs."""
+    layers, a built shape, k-octet and / or fp32 outputs.  Any pixel count: the kernel guards every lane (the C ABI takes any N > 0,
+    tests/test_gpu_chain_descriptors.py part B), so P % 4 is no condition here -- the engine's fp16 hand-over, which produces X, has
+    its own (engine.hidden_f16_ok)."""
     cx = _cx(cx)
     if tail is None or not cx.sk_tail or cx.precision not in (PRECISION_F16X2, PRECISION_F16) or not (cx.hidden_f16 and cx.hidden_koct):
         return False
-    if not (X.f16 and not X.koct and X.group == 0 and Y.group == 0 and X.rows == tail.C and Y.rows == tail.M2 and X.P % 4 == 0):
+    if not (X.f16 and not X.koct and X.group == 0 and Y.group == 0 and X.rows == tail.C and Y.rows == tail.M2):
         return False
     if Y.f16 and not Y.koct:
         return False
@@ -686,12 +688,13 @@ PAIR_SHAPES = {1: {(128, 128), (256, 256), (324, 324), (384, 384)},
 
 def ffn_pair_ok(pair: Optional[PackedPair], X: Planes, mode: int, cx: Optional["Ctx"] = None) -> bool:
     """Does sf_ffn_pair run this FFN?  fp16-activation arithmetic with k-octet hand-over, a k-octet operand (the planes themselves
-    or their copy; grouped '(B T) C -> B (T C)' views in groups of a multiple of 32 rows), one of the built shapes."""
+    or their copy; grouped '(B T) C -> B (T C)' views in groups of a multiple of 32 rows), one of the built shapes.  Any pixel count
+    (sf_ffn_pair takes any N > 0: tests/test_gpu_chain_descriptors.py part B)."""
     cx = _cx(cx)
     if pair is None or cx.precision not in (PRECISION_F16X2, PRECISION_F16) or not (cx.shadows and cx.hidden_f16 and cx.hidden_koct):
         return False
     src = X if (X.f16 and X.koct) else X.shadow
-    if src is None or X.P % 4 or (src.group and (src.group % 32 or pair.K1 % src.group)):
+    if src is None or (src.group and (src.group % 32 or pair.K1 % src.group)):
         return False
     pm = pair.products(cx)
     return (pair.K1, pair.M2) in PAIR_SHAPES[mode] and pm in ((1, 1), (2, 1), (2, 2))

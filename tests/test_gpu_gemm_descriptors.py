@@ -14,10 +14,10 @@ import torch
 import torch.nn.functional as F
 
 from tests import gemm_cases as gc
+from tests.guarded import SENTINEL, Guarded, _operand, _output
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 1234.5
 TOL = {"fp32": 3e-5, "f16x3": 3e-5, "f16x2": 5e-5, "f16": 5e-5}
 SPLIT_PRECS = ("f16x3", "f16x2", "f16")
 
@@ -32,79 +32,6 @@ def dev():
 def _prec(name):
     from streamflow_amd import ops
     return {"fp32": ops.PRECISION_FP32, "f16x3": ops.PRECISION_F16X3, "f16x2": ops.PRECISION_F16X2, "f16": ops.PRECISION_F16}[name]
-
-
-class Guarded:
-    """A [batch][rows][cols] view (row r of image z at off + z*stride + row_off(r), row_off(r) = r*ld, or in groups of `group`
-    rows `group_stride` apart) inside a flat buffer filled with `fill`.  The buffer ends with the last image's stride, so no
-    descriptor built from the view can span past it."""
-
-    def __init__(self, dev, batch, rows, cols, off, ld, stride, fill, dtype=torch.float32, group=0, group_stride=0):
-        assert ld >= cols and off >= 0
-        last_row = ((rows - 1) // group) * group_stride + ((rows - 1) % group) * ld if group else (rows - 1) * ld
-        assert stride >= last_row + cols
-        self.off, self.ld, self.stride, self.dtype, self.group_stride = off, ld, stride, dtype, group_stride
-        self.buf = torch.full((off + batch * stride,), fill, dtype=dtype, device=dev)
-        z = np.arange(batch)[:, None, None]
-        r = np.arange(rows)[None, :, None]
-        c = np.arange(cols)[None, None, :]
-        roff = (r // group) * group_stride + (r % group) * ld if group else r * ld
-        self.idx = torch.from_numpy((off + z * stride + roff + c).reshape(-1)).to(dev)
-        self.shape = (batch, rows, cols)
-        self.inside = torch.zeros(self.buf.numel(), dtype=torch.bool, device=dev)
-        self.inside[self.idx] = True
-
-    def put(self, t):
-        self.buf[self.idx] = t.to(device=self.buf.device, dtype=self.dtype).reshape(-1)
-        self.snap = self.buf.clone()
-        return self
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.buf.element_size() * self.off
-
-    def region(self):
-        return self.buf[self.idx].view(self.shape)
-
-    def outside_unchanged(self, before=None):
-        """Every element outside the view is bitwise what it was (the fill, or the snapshot taken by put())."""
-        ref = getattr(self, "snap", None) if before is None else before
-        if ref is None:
-            ref = torch.full_like(self.buf, SENTINEL)
-        a, b = self.buf[~self.inside], ref[~self.inside]
-        return bool(torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a.view(torch.int16),
-                                b.view(torch.int32) if b.dtype == torch.float32 else b.view(torch.int16)))
-
-
-def _operand(dev, rng, t, unaligned, dtype=torch.float32):
-    """Place logical [batch][rows][cols] data t in a NaN-poisoned allocation: ld padding, 1-3 extra rows after each image,
-    base 0 or (unaligned) 1-3 floats off 16 bytes (2-6 halves for fp16: a stored-fp16 B needs 4-byte alignment)."""
-    batch, rows, cols = t.shape
-    q = 8 if dtype == torch.float16 else 4                      # elements per 16 bytes
-    if unaligned:
-        off = int(rng.choice([2, 4, 6])) if dtype == torch.float16 else int(rng.integers(1, 4))
-        ld = cols + (cols % 2 + int(rng.choice([0, 2, 4])) if dtype == torch.float16 else int(rng.integers(1, 6)))   # even
-    else:
-        off, ld = q * int(rng.integers(0, 2)), -(-cols // q) * q + q * int(rng.integers(0, 3))
-    stride = (rows + int(rng.integers(1, 4))) * ld
-    stride = -(-stride // q) * q if not unaligned else stride + int(rng.integers(0, 3))
-    return Guarded(dev, batch, rows, cols, off, ld, stride, float("nan"), dtype).put(t)
-
-
-def _output(dev, rng, batch, rows, cols, unaligned, fill=SENTINEL, group=0):
-    """Output / residual placement: ld > cols, image stride > rows * ld (+ a gap between row groups for a grouped view)."""
-    if unaligned:
-        off, ld = int(rng.integers(1, 4)), cols + int(rng.integers(1, 6))
-    else:
-        off, ld = 4 * int(rng.integers(0, 2)), -(-(cols + 1) // 4) * 4 + 4 * int(rng.integers(0, 2))
-    gs = 0
-    if group:
-        gs = group * ld + 4 * int(rng.integers(1, 4))
-        span = ((rows - 1) // group) * gs + ((rows - 1) % group) * ld + cols
-    else:
-        span = rows * ld
-    stride = span + 4 * int(rng.integers(1, 4))
-    return Guarded(dev, batch, rows, cols, off, ld, stride, fill, group=group, group_stride=gs)
 
 
 def _epilogue(epi, v, R, dw_w, dw_b, gamma):
