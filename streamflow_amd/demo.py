@@ -3,7 +3,8 @@
 
 The demo slides a window of T frames with stride T-1 over the video; the last window re-uses the final T frames
 and drops the flow fields that an earlier window already produced (``flags == -1``).  Every consecutive frame pair
-(j, j+1) therefore gets exactly one flow field, in order.
+(j, j+1) therefore gets exactly one flow field, in order.  The schedule is defined once, in video.py (`clip_count`, `clip_start`);
+`group_clips` is its view with the demo's keep flags.
 """
 from __future__ import annotations
 
@@ -12,23 +13,15 @@ from typing import Callable, List, Sequence, Tuple
 import torch
 
 from .utils import InputPadder
+from .video import clip_count, clip_start
 
 
 def group_clips(n_frames: int, T: int = 4) -> List[Tuple[int, List[bool]]]:
-    """[(first frame of the window, keep[k] for each of its T-1 pairs)] -- the demo's window / flag schedule, in closed form:
-    `full = (n - 1) // (T - 1)` whole windows start at 0, T - 1, 2 (T - 1), ... and keep every pair; if pairs are left over
-    (`(n - 1) % (T - 1) != 0`) ONE more window is aligned to the end of the video (start n - T) and keeps only the pairs that start
-    at or behind frame `full * (T - 1)`, the first one no earlier window has produced."""
-    if T < 2 or n_frames < T:
-        raise ValueError(f"need at least T={T} >= 2 frames, got {n_frames}")
-    step = T - 1
-    full = (n_frames - 1) // step
-    out = [(s * step, [True] * step) for s in range(full)]
-    done = full * step                                   # pairs 0 .. done - 1 are covered
-    if done < n_frames - 1:
-        start = n_frames - T
-        out.append((start, [start + k >= done for k in range(step)]))
-    return out
+    """[(first frame of the window, keep[k] for each of its T-1 pairs)] -- the demo's window / flag schedule, as a view of
+    video.clip_count / clip_start: window c keeps the pairs that start at or behind frame c (T - 1), the first one no earlier
+    window has produced (every pair but for the tail window, which is aligned to the end of the video)."""
+    starts = [clip_start(c, n_frames, T) for c in range(clip_count(n_frames, T))]
+    return [(start, [start + k >= c * (T - 1) for k in range(T - 1)]) for c, start in enumerate(starts)]
 
 
 @torch.no_grad()

@@ -33,9 +33,11 @@
 -> list of nframes - 1 flows [1,2,H,W]`` (streamflow_amd.SKFlow_MF8, or the CPU oracle wrapped the same way in the tests); with
 ``clips_per_step > 1`` it is called as video.predict_video calls it (``model.forward_normalised(clips, iters)``, else
 ``model(clips)``, clips fp32 [k, T, 3, Hp, Wp] in [-1, 1]) and must live on a GPU: there is no host fallback.
-Files are read with this package's own codecs (flow_io.py: PNG, .flo, KITTI 16-bit PNG; flo5.py: Spring's .flo5).  Host-side
-plumbing: the kernels launched here are the tile blend of the tiled validators (ops.tile_blend) for models without
-``forward_tiled`` and the Spring scoring (ops.flow_score).
+Files are read with this package's own codecs (flow_io.py: PNG, .flo, KITTI 16-bit PNG; flo5.py: Spring's .flo5).  The frame
+reader, the per-clip model call (pad -> model -> unpad), the clip schedule and the walks over the three dataset trees are
+datasets.py's, shared with submit.py; ``sintel_clip_schedule`` is importable from here as before.  Host-side plumbing: the
+kernels launched here are the tile blend of the tiled validators (ops.tile_blend) for models without ``forward_tiled`` and the
+scoring kernels (ops.flow_score, ops.flow_score_batch).
 """
 from __future__ import annotations
 
@@ -47,42 +49,25 @@ import numpy as np
 import torch
 
 from . import flow_io
+from .datasets import (batched_call, frame_tensor, kitti_mf_clip, kitti_mf_sequences, model_device, padded_flows, read_clip,
+                       read_frame, run_clip, sintel_clip_schedule, sintel_scenes, spring_clips, spring_flow_file)
 from .utils import InputPadder
 
-
-def sintel_clip_schedule(n_images: int, nframes: int) -> List[Tuple[int, List[int]]]:
-    """[(first frame, frame ids)] of one scene (core/mf_datasets.py:1125-1149).  Clips start every nframes - 1 frames while a
-    whole clip fits; if frames are left over, ONE more clip is aligned to the end of the scene and the frames it shares
-    with the clips before it get id -1 (the pairs that start there are already scored).  Closed form: k = (n - 1) // (T - 1)
-    full clips start at 0, T - 1, ..; a tail clip exists iff (n - 1) % (T - 1) != 0 and starts at n - T."""
-    T = int(nframes)
-    if n_images < T or T < 2:
-        raise ValueError(f"a scene needs at least nframes = {T} >= 2 images, got {n_images}")
-    full = (n_images - 1) // (T - 1)
-    out = [(s * (T - 1), list(range(s * (T - 1), s * (T - 1) + T))) for s in range(full)]
-    covered = full * (T - 1)                          # first frame whose outgoing pair is not scored yet
-    if covered < n_images - 1:
-        first = n_images - T
-        out.append((first, [-1 if j < covered else j for j in range(first, n_images)]))
-    return out
+_image = frame_tensor                                                    # a PNG frame as float [3, H, W] in 0..255
 
 
-def _image(path: str) -> torch.Tensor:
-    img = flow_io.read_png(path)
-    if img.ndim == 2:
-        img = np.repeat(img[:, :, None], 3, axis=2)
-    return torch.from_numpy(np.ascontiguousarray(img[:, :, :3]).astype(np.uint8)).permute(2, 0, 1).float()
+def _occlusion(path: str, hw: Tuple[int, int]) -> np.ndarray:
+    m = flow_io.read_png(path)
+    if m.ndim != 2 or m.dtype != np.uint8 or tuple(m.shape) != tuple(hw):
+        raise RuntimeError(f"{path}: an occlusion map is an 8-bit gray PNG of {hw[0]} x {hw[1]}, got {m.dtype} {m.shape}")
+    return np.ascontiguousarray(m)
 
 
-def _scenes(image_root: str) -> List[str]:
-    return sorted(d for d in os.listdir(image_root) if os.path.isdir(os.path.join(image_root, d)))
-
-
-def _device_of(model) -> torch.device:
-    try:
-        return next(model.parameters()).device
-    except (AttributeError, StopIteration, TypeError):
-        return torch.device("cpu")
+def _need_gpu(what: str, dev: torch.device) -> torch.device:
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError(f"{what}: clips_per_step > 1 runs on the GPU (device {dev}, GPU available: {torch.cuda.is_available()}); "
+                           "there is no CPU fallback -- clips_per_step=1 is the host-side path")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
 
 
 @torch.no_grad()
@@ -90,35 +75,88 @@ def sintel_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
                   dstypes: Sequence[str] = ("clean", "final"), device: Optional[torch.device] = None, clips_per_step: int = 1,
                   occ: bool = False) -> Dict[str, Dict[str, float]]:
     """Per render pass: {'epe', '1px', '3px', '5px', 'pairs'} over every scored pair of every scene.  clips_per_step > 1: that many
-    clips per model call, scored on the GPU (_sintel_report_scored; adds 'pixels'); occ: also 'epe_occ', 'epe_noc', 'occ_pixels'
-    from the scenes' occlusion maps."""
-    dev = device or _device_of(model)
-    if int(clips_per_step) != 1 or occ:
-        return _sintel_report_scored(model, iters, root, nframes, dstypes, dev, int(clips_per_step), bool(occ))
+    clips per model call, scored on the GPU (adds 'pixels'); occ: also 'epe_occ', 'epe_noc', 'occ_pixels' from the scenes'
+    occlusion maps.
+
+    Two scorers, which differ in the last digits.  clips_per_step == 1 without occ is the reference's: the flows go to the host,
+    the per-pixel EPE of every pair is kept and flow_io.sintel_metrics reduces the lot, pass by pass.  Everything else goes
+    through the EVAL accumulator (scoring.py), one row per scored pair: device flows by ops.flow_score_batch, host flows (a CPU
+    model) by scoring.score_host_fields with the same arithmetic; the device rows are copied to the host once, at the end of the
+    report.  clips_per_step > 1: per scene, the uint8 frames (each decoded once) go through video.predict_video and every batch's
+    flows are scored as they arrive (its `sink`), so neither a flow nor a whole scene's flows leave the GPU or stay on it."""
+    from . import ops, scoring, video
+    dev = device or model_device(model, torch.device("cpu"))
+    clips_per_step, occ = int(clips_per_step), bool(occ)
+    per_pixel = clips_per_step == 1 and not occ
+    if clips_per_step < 1:
+        raise ValueError(f"clips_per_step must be at least 1, got {clips_per_step}")
+    if clips_per_step > 1:
+        dev = _need_gpu("sintel_report", dev)
     report = {}
+    rows = {d: [] for d in dstypes}                  # per pass: per-pixel EPE arrays, or [k, EVAL_LEN] arrays (host) / tensors (device)
     for dstype in dstypes:
-        image_root = os.path.join(root, "training", dstype)
-        flow_root = os.path.join(root, "training", "flow")
-        epe_list = []
-        for scene in _scenes(image_root):
-            imgs = sorted(glob.glob(os.path.join(image_root, scene, "*.png")))
-            flos = sorted(glob.glob(os.path.join(flow_root, scene, "*.flo")))
-            if len(flos) != len(imgs) - 1:
-                raise RuntimeError(f"{scene}: {len(imgs)} frames need {len(imgs) - 1} .flo files, found {len(flos)}")
+        for scene, imgs, flos, occs in sintel_scenes(root, "training", dstype, flow=True, occ=occ):
+
+            def truth(pairs: Sequence[int]):
+                gts = [flow_io.read_flo(flos[j]) for j in pairs]
+                return gts, ([_occlusion(occs[j], gts[0].shape[:2]) for j in pairs] if occ else None)
+
+            if clips_per_step > 1:
+                acc = torch.zeros(len(flos), scoring.EVAL_LEN, dtype=torch.float64, device=dev)
+
+                def score(first_pair: int, flows: torch.Tensor, acc=acc, truth=truth) -> None:
+                    gts, masks = truth(range(first_pair, first_pair + flows.shape[0]))
+                    g = torch.from_numpy(np.stack(gts)).to(flows.device)
+                    m = None if masks is None else list(torch.from_numpy(np.stack(masks)).to(flows.device))
+                    ops.flow_score_batch(list(flows), list(g), acc[first_pair:first_pair + flows.shape[0]], "flo", m)
+
+                video.predict_video(model, [read_frame(p) for p in imgs], T=nframes, iters=iters, clips_per_step=clips_per_step,
+                                    mode="sintel", device=dev, sink=score)
+                rows[dstype].append(acc)
+                continue
             for first, ids in sintel_clip_schedule(len(imgs), nframes):
-                images = [_image(p)[None].to(dev) for p in imgs[first:first + nframes]]
-                padder = InputPadder(images[0].shape)
-                flows = model(padder.pad_list(images), iters=iters, test_mode=True)
-                flows = [padder.unpad(f[0]).float().cpu() for f in flows]
-                for i in range(nframes - 1):
-                    if ids[i] == -1:
-                        continue
-                    gt = torch.from_numpy(flow_io.read_flo(flos[first + i])).permute(2, 0, 1).float()
-                    epe_list.append(torch.sum((flows[i] - gt) ** 2, dim=0).sqrt().view(-1).numpy())
-        epe_all = np.concatenate(epe_list)
-        m = flow_io.sintel_metrics(epe_all)
-        m["pairs"] = len(epe_list)
+                flows = run_clip(model, imgs[first:first + nframes], dev, iters)
+                keep = [i for i in range(nframes - 1) if ids[i] != -1]
+                if per_pixel:
+                    flows = [f.float().cpu() for f in flows]
+                    for i in keep:
+                        gt = torch.from_numpy(flow_io.read_flo(flos[first + i])).permute(2, 0, 1).float()
+                        rows[dstype].append(torch.sum((flows[i] - gt) ** 2, dim=0).sqrt().view(-1).numpy())
+                    continue
+                preds = [flows[i].float() for i in keep]
+                gts, masks = truth([first + i for i in keep])
+                if preds[0].is_cuda:
+                    d = preds[0].device
+                    acc = torch.zeros(len(keep), scoring.EVAL_LEN, dtype=torch.float64, device=d)
+                    ops.flow_score_batch(preds, [torch.from_numpy(g).to(d) for g in gts], acc, "flo",
+                                         None if masks is None else [torch.from_numpy(m).to(d) for m in masks])
+                else:
+                    acc = np.zeros((len(keep), scoring.EVAL_LEN), np.float64)
+                    for j, pred in enumerate(preds):
+                        scoring.score_host_fields(pred.numpy(), gts[j], acc[j], "flo", None if masks is None else masks[j])
+                rows[dstype].append(acc)
+        if per_pixel:
+            m = flow_io.sintel_metrics(np.concatenate(rows[dstype]))
+            m["pairs"] = len(rows[dstype])
+            print("Validation (%s) EPE: %f, 1px: %f, 3px: %f, 5px: %f" % (dstype, m["epe"], m["1px"], m["3px"], m["5px"]))
+            report[dstype] = m
+    if per_pixel:
+        return report
+    on_dev = [r for d in dstypes for r in rows[d] if isinstance(r, torch.Tensor)]
+    if on_dev:                                                          # one copy to the host for the whole report
+        host = torch.cat([r.to(on_dev[0].device) for r in on_dev]).cpu().numpy()
+        parts = iter(np.split(host, np.cumsum([r.shape[0] for r in on_dev])[:-1]))
+        rows = {d: [next(parts) if isinstance(r, torch.Tensor) else r for r in rows[d]] for d in dstypes}
+    for dstype in dstypes:
+        if not rows[dstype]:
+            raise RuntimeError(f"sintel_report: no pairs scored under {os.path.join(root, 'training', dstype)}")
+        m = scoring.sintel_from(np.concatenate(rows[dstype]))
         print("Validation (%s) EPE: %f, 1px: %f, 3px: %f, 5px: %f" % (dstype, m["epe"], m["1px"], m["3px"], m["5px"]))
+        if occ:
+            print("Occ epe: %f, Noc epe: %f" % (m["epe_occ"], m["epe_noc"]))
+        else:
+            for k in ("epe_occ", "epe_noc", "occ_pixels"):
+                del m[k]
         report[dstype] = m
     return report
 
@@ -143,112 +181,6 @@ def validate_sintel_occ_mf(model: Callable, iters: int = 6, root: str = "/data/S
     return {k: v["epe"] for k, v in rep.items()}
 
 
-def _frame_u8(path: str) -> np.ndarray:
-    """A PNG frame as uint8 [H, W, 3] (grey replicated, alpha dropped: what _image makes of it, before the conversion to float)."""
-    img = flow_io.read_png(path)
-    if img.ndim == 2:
-        img = np.repeat(img[:, :, None], 3, axis=2)
-    return np.ascontiguousarray(img[:, :, :3]).astype(np.uint8)
-
-
-def _occlusion(path: str, hw: Tuple[int, int]) -> np.ndarray:
-    m = flow_io.read_png(path)
-    if m.ndim != 2 or m.dtype != np.uint8 or tuple(m.shape) != tuple(hw):
-        raise RuntimeError(f"{path}: an occlusion map is an 8-bit gray PNG of {hw[0]} x {hw[1]}, got {m.dtype} {m.shape}")
-    return np.ascontiguousarray(m)
-
-
-def _need_gpu(what: str, dev: torch.device) -> torch.device:
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError(f"{what}: clips_per_step > 1 runs on the GPU (device {dev}, GPU available: {torch.cuda.is_available()}); "
-                           "there is no CPU fallback -- clips_per_step=1 is the host-side path")
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-
-
-def _sintel_report_scored(model: Callable, iters: int, root: str, nframes: int, dstypes: Sequence[str], dev: torch.device,
-                          clips_per_step: int, occ: bool) -> Dict[str, Dict[str, float]]:
-    """sintel_report through the EVAL accumulator (scoring.py): one row per scored pair.  clips_per_step > 1: per scene, the uint8
-    frames (each decoded once) go through video.predict_video and every batch's flows are scored as they arrive (its `sink`), so
-    neither a flow nor a whole scene's flows leave the GPU or stay on it.  clips_per_step == 1: the per-clip loop of sintel_report,
-    device flows scored by ops.flow_score_batch, host flows (a CPU model) by scoring.score_host_fields with the same arithmetic.
-    The device rows are copied to the host once, at the end of the report."""
-    from . import ops, scoring, video
-    if clips_per_step < 1:
-        raise ValueError(f"clips_per_step must be at least 1, got {clips_per_step}")
-    if clips_per_step > 1:
-        dev = _need_gpu("sintel_report", dev)
-    rows = {d: [] for d in dstypes}                                      # per pass: [k, EVAL_LEN] arrays (host) / tensors (device)
-    for dstype in dstypes:
-        image_root = os.path.join(root, "training", dstype)
-        flow_root = os.path.join(root, "training", "flow")
-        occ_root = os.path.join(root, "training", "occlusions")
-        for scene in _scenes(image_root):
-            imgs = sorted(glob.glob(os.path.join(image_root, scene, "*.png")))
-            flos = sorted(glob.glob(os.path.join(flow_root, scene, "*.flo")))
-            if len(flos) != len(imgs) - 1:
-                raise RuntimeError(f"{scene}: {len(imgs)} frames need {len(imgs) - 1} .flo files, found {len(flos)}")
-            occs = sorted(glob.glob(os.path.join(occ_root, scene, "*.png"))) if occ else None
-            if occ and len(occs) != len(flos):
-                raise RuntimeError(f"{scene}: {len(flos)} .flo files need as many occlusion maps under {occ_root}, found {len(occs)}")
-
-            def truth(pairs: Sequence[int]):
-                gts = [flow_io.read_flo(flos[j]) for j in pairs]
-                return gts, ([_occlusion(occs[j], gts[0].shape[:2]) for j in pairs] if occ else None)
-
-            if clips_per_step > 1:
-                acc = torch.zeros(len(flos), scoring.EVAL_LEN, dtype=torch.float64, device=dev)
-
-                def score(first_pair: int, flows: torch.Tensor, acc=acc, truth=truth) -> None:
-                    gts, masks = truth(range(first_pair, first_pair + flows.shape[0]))
-                    g = torch.from_numpy(np.stack(gts)).to(flows.device)
-                    m = None if masks is None else list(torch.from_numpy(np.stack(masks)).to(flows.device))
-                    ops.flow_score_batch(list(flows), list(g), acc[first_pair:first_pair + flows.shape[0]], "flo", m)
-
-                video.predict_video(model, [_frame_u8(p) for p in imgs], T=nframes, iters=iters, clips_per_step=clips_per_step,
-                                    mode="sintel", device=dev, sink=score)
-                rows[dstype].append(acc)
-                continue
-            for first, ids in sintel_clip_schedule(len(imgs), nframes):
-                images = [_image(p)[None].to(dev) for p in imgs[first:first + nframes]]
-                padder = InputPadder(images[0].shape)
-                flows = model(padder.pad_list(images), iters=iters, test_mode=True)
-                keep = [i for i in range(nframes - 1) if ids[i] != -1]
-                preds = [padder.unpad(flows[i][0]).float() for i in keep]
-                gts, masks = truth([first + i for i in keep])
-                if preds[0].is_cuda:
-                    d = preds[0].device
-                    acc = torch.zeros(len(keep), scoring.EVAL_LEN, dtype=torch.float64, device=d)
-                    ops.flow_score_batch(preds, [torch.from_numpy(g).to(d) for g in gts], acc, "flo",
-                                         None if masks is None else [torch.from_numpy(m).to(d) for m in masks])
-                else:
-                    acc = np.zeros((len(keep), scoring.EVAL_LEN), np.float64)
-                    for j, pred in enumerate(preds):
-                        scoring.score_host_fields(pred.numpy(), gts[j], acc[j], "flo", None if masks is None else masks[j])
-                rows[dstype].append(acc)
-    # one copy to the host for the whole report
-    on_dev = [(d, i) for d in dstypes for i, r in enumerate(rows[d]) if isinstance(r, torch.Tensor)]
-    if on_dev:
-        host = torch.cat([rows[d][i].to(rows[on_dev[0][0]][on_dev[0][1]].device) for d, i in on_dev]).cpu().numpy()
-        at = 0
-        for d, i in on_dev:
-            k = rows[d][i].shape[0]
-            rows[d][i] = host[at:at + k]
-            at += k
-    report = {}
-    for dstype in dstypes:
-        if not rows[dstype]:
-            raise RuntimeError(f"sintel_report: no pairs scored under {os.path.join(root, 'training', dstype)}")
-        m = scoring.sintel_from(np.concatenate(rows[dstype]))
-        print("Validation (%s) EPE: %f, 1px: %f, 3px: %f, 5px: %f" % (dstype, m["epe"], m["1px"], m["3px"], m["5px"]))
-        if occ:
-            print("Occ epe: %f, Noc epe: %f" % (m["epe_occ"], m["epe_noc"]))
-        else:
-            for k in ("epe_occ", "epe_noc", "occ_pixels"):
-                del m[k]
-        report[dstype] = m
-    return report
-
-
 @torch.no_grad()
 def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str] = None, nframes: int = 3,
                       device: Optional[torch.device] = None, clips_per_step: int = 1) -> Dict[str, float]:
@@ -256,32 +188,19 @@ def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str]
     clips_per_step > 1: up to that many sequences of one frame size per model call, scored on the GPU (_kitti_batched)."""
     if multi_root is None:
         raise ValueError("validate_kitti_mf: multi_root (the multi-frame KITTI-2015 tree) is required")
-    dev = device or _device_of(model)
-    image_root = os.path.join(multi_root, "training", "image_2")
-    flow_root = os.path.join(multi_root, "training", "flow_occ")
-    seqs = sorted(os.path.basename(p)[:6] for p in glob.glob(os.path.join(flow_root, "??????_10.png")))
-    if not seqs:
-        raise RuntimeError(f"no ground truth under {flow_root}")
+    dev = device or model_device(model, torch.device("cpu"))
+    image_root, flow_root, seqs = kitti_mf_sequences(multi_root, "training")
     if int(clips_per_step) != 1:
         return _kitti_batched(model, iters, image_root, flow_root, seqs, nframes, dev, int(clips_per_step))
-    out_list, epe_list = [], []
-    for seq in seqs:
-        images = [_image(os.path.join(image_root, "%s_%02d.png" % (seq, i)))[None].to(dev) for i in range(12 - nframes, 12)]
-        gt_np, valid_np = flow_io.read_flow_kitti(os.path.join(flow_root, seq + "_10.png"))
-        gt = torch.from_numpy(gt_np).permute(2, 0, 1).float()
-        valid = torch.from_numpy(valid_np)
-        padder = InputPadder(images[0].shape, mode="kitti")
-        flows = model(padder.pad_list(images), iters=iters, test_mode=True)
-        flow = padder.unpad(flows[nframes - 2][0]).float().cpu()          # only the last pair (frames 10 -> 11) has ground truth
-        epe = torch.sum((flow - gt) ** 2, dim=0).sqrt().view(-1)
-        mag = torch.sum(gt ** 2, dim=0).sqrt().view(-1)
-        val = valid.view(-1) >= 0.5
-        out = ((epe > 3.0) & ((epe / mag) > 0.05)).float()
-        epe_list.append(epe[val].mean().item())
-        out_list.append(out[val].numpy())
-    epe = float(np.mean(np.array(epe_list)))
-    f1 = float(100 * np.mean(np.concatenate(out_list)))
-    print("Validation KITTI: %f, %f" % (epe, f1))
+
+    def pairs():
+        for seq in seqs:
+            images = read_clip(kitti_mf_clip(image_root, seq, nframes), dev)
+            gt, valid = _kitti_gt(os.path.join(flow_root, seq + "_10.png"))
+            flows = padded_flows(model, images, iters, mode="kitti")
+            yield flows[nframes - 2].float().cpu(), gt, valid             # only the last pair (frames 10 -> 11) has ground truth
+
+    epe, f1 = _kitti_scores(pairs())
     return {"kitti_epe": epe, "kitti_f1": f1}
 
 
@@ -297,7 +216,7 @@ def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str,
         raise ValueError(f"clips_per_step must be at least 1, got {clips_per_step}")
     dev = _need_gpu("validate_kitti_mf", dev)
     T = int(nframes)
-    call = (lambda x: model.forward_normalised(x, iters)) if hasattr(model, "forward_normalised") else model
+    call = batched_call(model, iters)
     rows, pending = [], []                                              # device rows [k, EVAL_LEN]; (frames [T, H, W, 3], samples)
 
     def flush() -> None:
@@ -324,7 +243,7 @@ def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str,
 
     with torch.cuda.device(dev):
         for seq in seqs:
-            frames = np.stack([_frame_u8(os.path.join(image_root, "%s_%02d.png" % (seq, i))) for i in range(12 - T, 12)])
+            frames = np.stack([read_frame(p) for p in kitti_mf_clip(image_root, seq, T)])
             path = os.path.join(flow_root, seq + "_10.png")
             smp = flow_io.read_png(path)
             if smp.ndim != 3 or smp.shape[2] < 3 or smp.dtype != np.uint16:
@@ -341,13 +260,6 @@ def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str,
 
 
 # ---- Spring (evaluate_mf.py:50-102, core/mf_datasets.py:99-213) ---------------------------------------------------------------
-def _spring_gt_path(scene_dir: str, direction: str, cam: str, n: int, index: int) -> str:
-    """Ground-truth file of pair `index` of the (forward or reversed) frame list: forward flow_FW_<cam>_{index + 1:04d},
-    backward flow_BW_<cam>_{n - index:04d} (mf_datasets.py:126-127, :148-149)."""
-    number = index + 1 if direction == "FW" else n - index
-    return os.path.join(scene_dir, f"flow_{direction}_{cam}", f"flow_{direction}_{cam}_{number:04d}.flo5")
-
-
 @torch.no_grad()
 def spring_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", nframes: int = 3, device: Optional[torch.device] = None,
                   scenes: Optional[Sequence[str]] = ("0041",)) -> Dict[str, float]:
@@ -357,43 +269,34 @@ def spring_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
 
     Walks root/train/<scene>/frame_{left,right}/*.png: per scene (sorted), per camera (left, right), the forward clips, then the
     backward clips (the same frames reversed), both on sintel_clip_schedule; pair k of a clip starting at a is scored against
-    ground-truth file a + k (_spring_gt_path), subsampled [::2, ::2] as the reference does; pairs with frame id -1 are skipped.
-    Flows on the GPU are scored where they are by ops.flow_score into one device accumulator (one copy to the host at the end);
+    ground-truth file a + k (datasets.spring_flow_file), subsampled [::2, ::2] as the reference does; pairs with frame id -1 are
+    skipped.  Flows on the GPU are scored where they are by ops.flow_score into one device accumulator (one copy to the host at the end);
     host flows (a CPU model) by scoring.score_host, with the same arithmetic (scoring.py states how both relate to the reference).
     Reference quirks kept: only scene 0041 by default (the hard-coded train / val split, mf_datasets.py:117; scenes=None scores
     every scene); the dataset's |flow| < 1000 valid maps are not used; 'epe' is NaN as soon as one ground-truth pixel is NaN."""
     from . import flo5, ops, scoring
-    dev = device or _device_of(model)
+    dev = device or model_device(model, torch.device("cpu"))
     train = os.path.join(root, "train")
-    names = [s for s in _scenes(train) if scenes is None or s in scenes]
     acc_host = np.zeros(scoring.LEN, np.float64)
     acc_dev = {}
     pairs = 0
     step = 2                                                            # SpringEval(subsample_groundtruth=True)
-    for scene in names:
-        scene_dir = os.path.join(train, scene)
-        for cam in ("left", "right"):
-            frames = sorted(glob.glob(os.path.join(scene_dir, f"frame_{cam}", "*.png")))
-            n = len(frames)
-            for direction, order in (("FW", frames), ("BW", frames[::-1])):
-                for first, ids in sintel_clip_schedule(n, nframes):
-                    images = [_image(p)[None].to(dev) for p in order[first:first + nframes]]
-                    padder = InputPadder(images[0].shape)
-                    flows = model(padder.pad_list(images), iters=iters, test_mode=True)
-                    for k in range(nframes - 1):
-                        if ids[k] == -1:
-                            continue
-                        gt = flo5.read_flo5(_spring_gt_path(scene_dir, direction, cam, n, first + k))
-                        pred = padder.unpad(flows[k][0])
-                        if pred.is_cuda:
-                            acc = acc_dev.get(pred.device)
-                            if acc is None:
-                                acc = acc_dev[pred.device] = torch.zeros(scoring.LEN, dtype=torch.float64, device=pred.device)
-                            ops.flow_score(pred.float(), torch.from_numpy(np.ascontiguousarray(gt, np.float32)).to(pred.device),
-                                           acc, step)
-                        else:
-                            scoring.score_host(pred.float().numpy(), gt, acc_host, step)
-                        pairs += 1
+    for scene, cam, direction, order, n, schedule in spring_clips(root, "train", nframes, only=scenes):
+        for first, ids in schedule:
+            flows = run_clip(model, order[first:first + nframes], dev, iters)
+            for k in range(nframes - 1):
+                if ids[k] == -1:
+                    continue
+                gt = flo5.read_flo5(os.path.join(train, scene, spring_flow_file(direction, cam, n, first + k)))
+                pred = flows[k]
+                if pred.is_cuda:
+                    acc = acc_dev.get(pred.device)
+                    if acc is None:
+                        acc = acc_dev[pred.device] = torch.zeros(scoring.LEN, dtype=torch.float64, device=pred.device)
+                    ops.flow_score(pred.float(), torch.from_numpy(np.ascontiguousarray(gt, np.float32)).to(pred.device), acc, step)
+                else:
+                    scoring.score_host(pred.float().numpy(), gt, acc_host, step)
+                pairs += 1
     if pairs == 0:
         raise RuntimeError(f"spring_report: no pairs scored under {train} (scenes={scenes})")
     for acc in acc_dev.values():
@@ -468,16 +371,12 @@ def validate_kitti_mf_tile(model: Callable, iters: int = 6, multi_root: Optional
     from .tiling import KITTI_MF_TILE, FixedHeightPadder
     if multi_root is None:
         raise ValueError("validate_kitti_mf_tile: multi_root (the multi-frame KITTI-2015 tree) is required")
-    dev = device or _device_of(model)
-    image_root = os.path.join(multi_root, "training", "image_2")
-    flow_root = os.path.join(multi_root, "training", "flow_occ")
-    seqs = sorted(os.path.basename(p)[:6] for p in glob.glob(os.path.join(flow_root, "??????_10.png")))
-    if not seqs:
-        raise RuntimeError(f"no ground truth under {flow_root}")
+    dev = device or model_device(model, torch.device("cpu"))
+    image_root, flow_root, seqs = kitti_mf_sequences(multi_root, "training")
 
     def pairs():
         for seq in seqs:
-            images = [_image(os.path.join(image_root, "%s_%02d.png" % (seq, i)))[None].to(dev) for i in range(12 - nframes, 12)]
+            images = read_clip(kitti_mf_clip(image_root, seq, nframes), dev)
             padder = FixedHeightPadder(images[0].shape, KITTI_MF_TILE[0], mode="replicate")
             flows = _tiled_flows(model, padder.pad_list(images), padder, KITTI_MF_TILE, iters, dev)
             gt, valid = _kitti_gt(os.path.join(flow_root, seq + "_10.png"))
@@ -497,7 +396,7 @@ def validate_kitti_tile(model: Callable, iters: int = 6, root: Optional[str] = N
     from .tiling import KITTI_TILE, FixedHeightPadder
     if root is None:
         raise ValueError("validate_kitti_tile: root (the KITTI-2015 tree) is required")
-    dev = device or _device_of(model)
+    dev = device or model_device(model, torch.device("cpu"))
     images1 = sorted(glob.glob(os.path.join(root, "training", "image_2", "*_10.png")))
     images2 = sorted(glob.glob(os.path.join(root, "training", "image_2", "*_11.png")))
     flows_gt = sorted(glob.glob(os.path.join(root, "training", "flow_occ", "*_10.png")))
@@ -506,7 +405,7 @@ def validate_kitti_tile(model: Callable, iters: int = 6, root: Optional[str] = N
 
     def pairs():
         for im1, im2, fl in zip(images1, images2, flows_gt):
-            images = [_image(p)[None].to(dev) for p in (im1, im2)]
+            images = read_clip((im1, im2), dev)
             padder = FixedHeightPadder(images[0].shape, KITTI_TILE[0], mode="zeros")
             flows = _tiled_flows(model, padder.pad(*images), padder, KITTI_TILE, None, dev)
             gt, valid = _kitti_gt(fl)

@@ -1370,7 +1370,7 @@ def frames_to_clips(frames: torch.Tensor, n: int, T: int, first_clip: int, n_cli
     on the GPU, [n_buf, H, W, 3] or [n_buf, 3, H, W] (any strides; `channels_last` decides when both readings fit, default: HWC if
     the last dimension is 3), holding the frames frame0 .. frame0 + n_buf - 1 of a video of `n` frames; pad = [left, right, top,
     bottom] as InputPadder._pad.  Returns fp32 [n_clips, T, 3, Hp, Wp] for the clips first_clip .. first_clip + n_clips - 1 of the
-    schedule in include/streamflow_hip.h (= demo.group_clips).  Enqueued on the current stream, no synchronisation."""
+    schedule in include/streamflow_hip.h (= video.clip_count / clip_start).  Enqueued on the current stream, no synchronisation."""
     if not frames.is_cuda:
         raise RuntimeError(f"frames_to_clips: frames must be on the GPU (got {frames.device}); there is no CPU fallback")
     if frames.dtype != torch.uint8 or frames.dim() != 4:

@@ -1,9 +1,9 @@
 """Leaderboard writers with the reference's signatures and file names (SURVEY.md row f3's last step).
 
 * ``create_sintel_submission_mf(args, model, iters, output_path, nframes)`` -- reference evaluate_mf.py:252-282 over
-  ``args.sintel_root/test/{clean,final}/<scene>/*.png``: the clip schedule of ``evaluate.sintel_clip_schedule``, pad -> model ->
-  unpad, and for every pair whose frame id is not -1 the flow as ``output_path/<dstype>/<scene>/frame%04d.flo`` (id + 1) and its
-  colour-wheel image as ``output_path/<dstype>/<scene>-<id + 1>.png``.
+  ``args.sintel_root/test/{clean,final}/<scene>/*.png``: the clip schedule of ``datasets.sintel_clip_schedule``, pad -> model ->
+  unpad (``datasets.run_clip``), and for every pair whose frame id is not -1 the flow as
+  ``output_path/<dstype>/<scene>/frame%04d.flo`` (id + 1) and its colour-wheel image as ``output_path/<dstype>/<scene>-<id + 1>.png``.
 * ``create_sintel_submission_mf_warmup`` -- evaluate_mf.py:286-323: the same, every clip warm-started from the previous clip's
   low-resolution flows (``demo.predict_clips_warm_start``, one chain per scene).
 * ``create_kitti_submission_mf(args, model, iters, output_path, nframes, vis_path)`` -- submit_mf.py:700-728 over
@@ -14,20 +14,21 @@
   ``args.spring_root/test/<scene>/frame_{left,right}/*.png``: forward and backward clips of every scene and camera, each flow as
   ``output_path/<scene>/flow_<FW|BW>_<cam>/flow_<FW|BW>_<cam>_%04d.flo5`` (flo5.write_flo5, gzip level 5); no colour images.
 
-``model`` is the reference's test-mode call (see evaluate.py).  The colour images of one clip are made on the device by ONE
+``model`` is the reference's test-mode call (see evaluate.py); the tree walks, the frame reader and the per-clip model call are
+datasets.py's, shared with evaluate.py.  The colour images of one clip are made on the device by ONE
 ``ops.flow_to_image`` call before the flows are copied to the host; ``vis=False`` launches no kernel, which lets the writers run
 with a CPU model.
 """
 from __future__ import annotations
 
-import glob
 import os
 from typing import Callable, List, Optional
 
 import torch
 
 from . import flow_io
-from .evaluate import _device_of, _image, _scenes, sintel_clip_schedule
+from .datasets import (kitti_mf_clip, kitti_mf_sequences, model_device, read_clip, run_clip, sintel_clip_schedule, sintel_scenes,
+                       spring_clips, spring_flow_file)
 from .utils import InputPadder
 
 
@@ -58,27 +59,16 @@ def _write_sintel_clip(flows: List[torch.Tensor], ids: List[int], output_path: s
             flow_io.write_png(os.path.join(output_path, dstype, "%s-%d.png" % (scene, ids[i] + 1)), images[i])
 
 
-def _sintel_scenes(args, dstype: str, nframes: int):
-    """(scene, sorted frame paths, clip schedule) of every scene of the test split."""
-    image_root = os.path.join(args.sintel_root, "test", dstype)
-    for scene in _scenes(image_root):
-        imgs = sorted(glob.glob(os.path.join(image_root, scene, "*.png")))
-        yield scene, imgs, sintel_clip_schedule(len(imgs), nframes)
-
-
 @torch.no_grad()
 def create_sintel_submission_mf(args, model: Callable, iters: int, output_path: str = "sintel_submission", nframes: int = 3,
                                 vis: bool = True, device: Optional[torch.device] = None) -> None:
     """Create the submission tree for the Sintel leaderboard (every clip from a cold start)."""
     _eval_mode(model)
-    dev = device or _device_of(model)
+    dev = device or model_device(model, torch.device("cpu"))
     for dstype in ("clean", "final"):
-        for scene, imgs, schedule in _sintel_scenes(args, dstype, nframes):
-            for first, ids in schedule:
-                images = [_image(p)[None].to(dev) for p in imgs[first:first + nframes]]
-                padder = InputPadder(images[0].shape)
-                flows = model(padder.pad_list(images), iters=iters, test_mode=True)
-                _write_sintel_clip([padder.unpad(f[0]) for f in flows], ids, output_path, dstype, scene, vis)
+        for scene, imgs, _, _ in sintel_scenes(args.sintel_root, "test", dstype):
+            for first, ids in sintel_clip_schedule(len(imgs), nframes):
+                _write_sintel_clip(run_clip(model, imgs[first:first + nframes], dev, iters), ids, output_path, dstype, scene, vis)
 
 
 @torch.no_grad()
@@ -90,14 +80,15 @@ def create_sintel_submission_mf_warmup(args, model: Callable, iters: int, output
     low-resolution fields).  Clips are read one at a time; the files of a scene are written when its chain is done."""
     from .demo import predict_clips_warm_start
     _eval_mode(model)
-    dev = device or _device_of(model)
+    dev = device or model_device(model, torch.device("cpu"))
     for dstype in ("clean", "final"):
-        for scene, imgs, schedule in _sintel_scenes(args, dstype, nframes):
+        for scene, imgs, _, _ in sintel_scenes(args.sintel_root, "test", dstype):
+            schedule = sintel_clip_schedule(len(imgs), nframes)
             padder = InputPadder(flow_io.read_png(imgs[0]).shape[:2])
 
             def clips():
                 for first, _ in schedule:
-                    yield padder.pad_list([_image(p)[None].to(dev) for p in imgs[first:first + nframes]])
+                    yield padder.pad_list(read_clip(imgs[first:first + nframes], dev))
 
             for (_, ids), flows in zip(schedule, predict_clips_warm_start(model, clips(), iters=iters)):
                 _write_sintel_clip([padder.unpad(f[0]) for f in flows], ids, output_path, dstype, scene, vis)
@@ -114,26 +105,16 @@ def create_spring_submission_mf(args, model: Callable, iters: int, output_path: 
     reference there are no colour images, and the default output_path is the reference's 'sintel_submission'."""
     from . import flo5
     _eval_mode(model)
-    dev = device or _device_of(model)
-    test_root = os.path.join(args.spring_root, "test")
-    for scene in _scenes(test_root):
-        for cam in ("left", "right"):
-            frames = sorted(glob.glob(os.path.join(test_root, scene, f"frame_{cam}", "*.png")))
-            n = len(frames)
-            for direction, order in (("FW", frames), ("BW", frames[::-1])):
-                output_dir = os.path.join(output_path, scene, f"flow_{direction}_{cam}")
-                os.makedirs(output_dir, exist_ok=True)
-                for first, ids in sintel_clip_schedule(n, nframes):
-                    images = [_image(p)[None].to(dev) for p in order[first:first + nframes]]
-                    padder = InputPadder(images[0].shape)
-                    flows = model(padder.pad_list(images), iters=iters, test_mode=True)
-                    assert len(flows) == len(ids) - 1
-                    for k, j in enumerate(ids[:-1]):
-                        if j == -1:
-                            continue
-                        number = j + 1 if direction == "FW" else n - j
-                        flo5.write_flo5(os.path.join(output_dir, f"flow_{direction}_{cam}_%04d.flo5" % number),
-                                        padder.unpad(flows[k][0]).permute(1, 2, 0).float().cpu().numpy(), compression_level=5)
+    dev = device or model_device(model, torch.device("cpu"))
+    for scene, cam, direction, order, n, schedule in spring_clips(args.spring_root, "test", nframes):
+        os.makedirs(os.path.join(output_path, scene, f"flow_{direction}_{cam}"), exist_ok=True)
+        for first, ids in schedule:
+            flows = run_clip(model, order[first:first + nframes], dev, iters)
+            assert len(flows) == len(ids) - 1
+            for k, j in enumerate(ids[:-1]):
+                if j != -1:
+                    flo5.write_flo5(os.path.join(output_path, scene, spring_flow_file(direction, cam, n, j)),
+                                    flows[k].permute(1, 2, 0).float().cpu().numpy(), compression_level=5)
 
 
 @torch.no_grad()
@@ -142,19 +123,13 @@ def create_kitti_submission_mf(args, model: Callable, iters: int, output_path: s
     """Create the submission folder for the KITTI-2015 leaderboard from the multi-frame test split: one 16-bit PNG per sequence
     (the flow of frames 10 -> 11).  Sequences are those present under ``testing/image_2`` (the reference walks 000000 .. 000199)."""
     _eval_mode(model)
-    dev = device or _device_of(model)
-    image_root = os.path.join(args.multi_root, "testing", "image_2")
-    seqs = sorted(os.path.basename(p)[:6] for p in glob.glob(os.path.join(image_root, "??????_10.png")))
-    if not seqs:
-        raise RuntimeError(f"no sequences under {image_root}")
+    dev = device or model_device(model, torch.device("cpu"))
+    image_root, _, seqs = kitti_mf_sequences(args.multi_root, "testing")
     os.makedirs(output_path, exist_ok=True)
     if vis_path is not None:
         os.makedirs(os.path.join(vis_path, "flow"), exist_ok=True)
     for seq in seqs:
-        images = [_image(os.path.join(image_root, "%s_%02d.png" % (seq, i)))[None].to(dev) for i in range(12 - nframes, 12)]
-        padder = InputPadder(images[0].shape)                    # default mode, as submit_mf.py:711 (not 'kitti')
-        flows = model(padder.pad_list(images), iters=iters, test_mode=True)
-        flow = padder.unpad(flows[-1][0])
+        flow = run_clip(model, kitti_mf_clip(image_root, seq, nframes), dev, iters)[-1]       # default mode, not 'kitti': submit_mf.py:711
         frame_name = seq + "_10.png"
         image = _colour([flow], [0])[0] if vis_path is not None else None
         flow_io.write_flow_kitti(os.path.join(output_path, frame_name), flow.permute(1, 2, 0).float().cpu().numpy())

@@ -5,8 +5,9 @@ from PNG files (`FrameDir`), or already on the GPU.  Per batch of clips: the uin
 they are device-resident), ONE sf_frames_to_clips launch normalises, replicate-pads and groups them into [n_clips, T, 3, Hp, Wp], the
 model runs once, ONE sf_clips_to_flows launch crops the kept flow fields into video order.  The host never holds a frame in fp32.
 
-The clip schedule (include/streamflow_hip.h, "video clips") is `demo.group_clips` in closed form; `clip_start`, `pair_clip` and
-`plan_batches` restate it on the host for the batching.  `demo.predict_frames` stays the one-clip-per-call host path.
+`clip_count`, `clip_start` and `pair_clip` are the one host-side definition of the clip schedule (include/streamflow_hip.h, "video
+clips": the kernels compute the same closed form); `demo.group_clips` and `datasets.sintel_clip_schedule` are views of it with the
+reference's keep flags and frame ids.  `demo.predict_frames` stays the one-clip-per-call host path.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import flow_io
+from .datasets import batched_call, model_device, read_frame
 from .utils import InputPadder
 
 MAX_PAIRS = 8               # SF_VIDEO_MAX_PAIRS: pair pointers one sf_clips_to_flows call takes
@@ -72,9 +73,8 @@ def _png_size(path: str) -> Tuple[int, int]:
 
 class FrameDir:
     """The PNG frames of a directory, sorted by name, as a lazy sequence of uint8 [H, W, 3] arrays: a frame is decoded
-    (flow_io.read_png) when it is indexed and not kept.  Grey frames are replicated to three channels and alpha is dropped, as
-    evaluate._image does.  All frames must have one size: the headers are compared when the object is made, the decoded arrays
-    again when they are read."""
+    (datasets.read_frame: grey replicated to three channels, alpha dropped) when it is indexed and not kept.  All frames must have
+    one size: the headers are compared when the object is made, the decoded arrays again when they are read."""
 
     def __init__(self, path: str, pattern: str = "*.png"):
         self.paths = sorted(glob.glob(os.path.join(path, pattern)))
@@ -91,10 +91,7 @@ class FrameDir:
     def __getitem__(self, i: int) -> np.ndarray:
         if isinstance(i, slice):
             raise TypeError("FrameDir is indexed by frame number")
-        img = flow_io.read_png(self.paths[i])
-        if img.ndim == 2 or img.shape[2] == 2:                           # grey, grey + alpha
-            img = np.repeat((img if img.ndim == 2 else img[:, :, 0])[:, :, None], 3, axis=2)
-        img = np.ascontiguousarray(img[:, :, :3]).astype(np.uint8)
+        img = read_frame(self.paths[i])
         if img.shape[:2] != self.hw:
             raise ValueError(f"{self.paths[i]}: frame size {img.shape[:2]} differs from {self.hw}")
         return img
@@ -165,13 +162,6 @@ class _Source:
         return torch.stack([f.cpu() for f in batch]).to(dev), True, lo
 
 
-def _model_device(model) -> Optional[torch.device]:
-    try:
-        return next(model.parameters()).device
-    except (AttributeError, StopIteration, TypeError):
-        return None
-
-
 @torch.no_grad()
 def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = None, clips_per_step: int = 8, mode: str = "sintel",
                   device=None, sink: Optional[Callable[[int, torch.Tensor], None]] = None) -> Optional[torch.Tensor]:
@@ -193,7 +183,7 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
         raise ValueError(f"predict_video: need at least T={T} frames, got {src.n}")
     batches = plan_batches(src.n, T, int(clips_per_step))
     if device is None:
-        device = src.stack.device if src.stack is not None and src.stack.is_cuda else _model_device(model)
+        device = src.stack.device if src.stack is not None and src.stack.is_cuda else model_device(model)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     dev = torch.device(device)
@@ -204,7 +194,7 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
         dev = torch.device("cuda", torch.cuda.current_device())
     H, W = src.hw
     pad = InputPadder((H, W), mode=mode)._pad
-    call = (lambda x: model.forward_normalised(x, iters)) if hasattr(model, "forward_normalised") else model
+    call = batched_call(model, iters)
     out = None if sink is not None else torch.empty(src.n - 1, 2, H, W, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         for first, k, f_lo, f_hi, p_lo, p_hi in batches:

@@ -10,7 +10,7 @@ from argparse import Namespace
 import numpy as np
 import torch
 
-from streamflow_amd import evaluate, flo5, flow_io, scoring, submit
+from streamflow_amd import datasets, evaluate, flo5, flow_io, scoring, submit
 from tests import score_cases as sc
 
 
@@ -130,8 +130,7 @@ def _touch_tree(root, scene, n):
 def test_pairs_and_files_match_the_reference_loops(tmp_path, monkeypatch):
     """For T = 2..6 and scenes of T..30 frames: the (pair, ground-truth file) set the validator scores equals the reference's, every
     file once; the submission writes exactly the reference's file names, every one once."""
-    monkeypatch.setattr(evaluate, "_image", _tag_image)
-    monkeypatch.setattr(submit, "_image", _tag_image)
+    monkeypatch.setattr(datasets, "read_frame", lambda path: _tag_image(path).permute(1, 2, 0).numpy().astype(np.uint8))
     scored, read, written = [], [], []
     monkeypatch.setattr(flo5, "read_flo5", lambda path: (read.append(path), np.zeros((8, 8, 2), np.float32))[1])
     monkeypatch.setattr(scoring, "score_host",
