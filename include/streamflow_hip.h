@@ -44,7 +44,9 @@ int sf_coords_grid(float* out, int batch, int ht, int wd, void* stream);
 
 /* ---- a4: bilinear_sampler  (core/utils/utils.py:65-79; F.grid_sample bilinear/zeros/align_corners)
  * img [M][C][Hi][Wi], coords [M][Ho][Wo][2] pixel (x,y)  ->  out [M][C][Ho][Wo].
- * mask_out (optional, may be NULL): [M][Ho][Wo][1] in-bounds indicator as the reference's mask=True. */
+ * mask_out (optional, may be NULL): [M][Ho][Wo][1] in-bounds indicator as the reference's mask=True.
+ * A tap outside the image is zero.  A non-finite coordinate (and one beyond +-1e6 pixels) samples zero, and the output is
+ * finite: the rule the lookup kernels follow for the same input. */
 int sf_bilinear_sampler(const float* img, const float* coords, float* out, float* mask_out,
                         int M, int C, int Hi, int Wi, int Ho, int Wo, void* stream);
 
@@ -495,7 +497,9 @@ int sf_layernorm_cm(const float* x, int64_t x_img_stride, const float* gamma, co
 /* ---- per-pixel attention over the T-1 tokens (timm Attention core, update.py:466-474) ----------
  * qkv [B*TT][3*C][P] (rows [q|k|v]) -> out [B*TT][C][P]; softmax(q k^T / sqrt(C)) v over t.
  * out_koct (optional, C % 32 == 0): the result as fp16 k-octet planes [B*TT][C/8][P][8] (SF_LAYOUT_F16_KOCT); out may
- * then be NULL. */
+ * then be NULL.  C % 4 == 0.  TT = 1..7; a TT outside that range returns SF_ERR_UNSUPPORTED.  TT = 4..7 is what clips of
+ * T >= 5 frames run: sf_temporal_block stops at TT = 3.  Both forms (this one and sf_temporal_attn_f16in) are tested over TT = 1..7
+ * (tests/test_gpu_glue_kernels.py). */
 int sf_temporal_attn(const float* qkv, float* out, void* out_koct, int B, int TT, int C, int P, void* stream);
 /* The same with qkv as fp16 ROWS [B*TT][3C][P] (what sf_gemm writes with c_f16 = 1): the config-2 hand-over -- the qkv GEMM
  * writes and this kernel reads half the bytes; scores, softmax and the weighted sum stay fp32. */

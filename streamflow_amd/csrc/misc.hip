@@ -181,12 +181,18 @@ __global__ __launch_bounds__(kBlock) void layernorm_cm_kernel(const float* x, in
     float mean = 0.f;
     for (int c = 0; c < C; ++c) mean += xp[(int64_t)c * P];
     mean /= (float)C;
-    float var = 0.f;
+    // Corrected two-pass: the running sum above rounds at ulp(C * mean) every step, and the mean's error moves every output of the
+    // column.  The deviations from that first mean are small numbers whose sum rounds at their own scale: it gives back what the
+    // first pass lost (it matters when |mean| is large against the spread).
+    float sd = 0.f, var = 0.f;
     for (int c = 0; c < C; ++c) {
         const float d = xp[(int64_t)c * P] - mean;
+        sd += d;
         var += d * d;
     }
-    const float rstd = 1.0f / sqrtf(var / (float)C + eps);
+    const float dm = sd / (float)C;
+    mean += dm;
+    const float rstd = 1.0f / sqrtf(fmaxf(var / (float)C - dm * dm, 0.f) + eps);
     for (int c = 0; c < C; ++c) yp[(int64_t)c * P] = (xp[(int64_t)c * P] - mean) * rstd * gamma[c] + beta[c];
 }
 
