@@ -293,7 +293,16 @@ int sf_splitk_combine(const float* partial, int64_t split_stride, int k_splits, 
  *       out_koct (optional): `out` a second time, rounded to fp16, as k-octet planes [16][P][8] per image
  *       (SF_LAYOUT_F16_KOCT, image stride in halves) -- the operand format of the GEMM that reads it next.
  * ws: caller-owned scratch of sf_gma_flash_ws_bytes(n_img, P) bytes, 16-byte aligned; must persist from pack_qk to the
- * last aggregate of the clip. */
+ * last aggregate of the clip.
+ * Established by tests/test_gpu_attn_kernels.py (P = 1 .. 641, image strides beyond dense, bases off the allocation):
+ *   sf_gma_flash_ws_bytes: exactly that many bytes suffice for every call below (nothing is read or written past them).
+ *   sf_gma_flash_pack_qk: writes `ws` only; every call (re)writes the header that names P and stats_qk_products.
+ *   sf_gma_flash_aggregate: use_stats = 1 with statistics of another product count, of another P (same rounded-up size), or of
+ *       stats_qk_products = 0 gives NaN in EVERY element of out and out_koct, never a silent result; image z of a batch is bitwise
+ *       the call on image z alone (n_img on the same side of the key-range split); the pipelined and the plain kernel agree
+ *       bitwise; out_koct is bitwise fp16(out); gamma = 0 returns mf exactly; a NaN in mf or in one query stays at that pixel.
+ *   sf_gma_flash_aggregate_f16v: bitwise sf_gma_flash_aggregate on fp32 planes whose rounding to fp16 gives those rows.
+ *   sf_gma_flash_project_v: for operands whose products and sums are exact in fp32, bitwise the aggregate of those v planes. */
 int64_t sf_gma_flash_ws_bytes(int n_img, int P);
 int sf_gma_flash_pack_qk(const float* qk, int64_t qk_img_stride, void* ws, int64_t ws_bytes, int n_img, int P,
                          float scale, int stats_qk_products, void* stream);
@@ -327,7 +336,10 @@ int sf_gma_flash_project_v(void* ws, int64_t ws_bytes, const void* x_koct, int64
  *   sf_gma_flash_store_p: once per clip, after sf_gma_flash_pack_qk(stats_qk_products = qk_products): writes pbuf.
  *   sf_gma_stored_aggregate: every iteration; out = mf + gamma / rowsum * v P^T.  v as in sf_gma_flash_aggregate (v_f16 = 1: fp16
  *       rows; v == NULL: the v planes of ws are current, sf_gma_flash_project_v).  With the same ws the result is bit-identical to
- *       sf_gma_flash_aggregate(use_stats = 1).  Weights stored by another pack call / product count poison the result (NaN). */
+ *       sf_gma_flash_aggregate(use_stats = 1).  Weights stored by another pack call / product count poison the result (NaN).
+ *   Established by tests/test_gpu_attn_kernels.py: sf_gma_stored_p_bytes bytes suffice exactly; sf_gma_flash_store_p writes pbuf and the
+ *   header of ws only; sf_gma_stored_aggregate without a store_p behind the last pack_qk, after a pack_qk for another P or with
+ *   stats_qk_products = 0, gives NaN in every element of out and out_koct -- split and unsplit key range alike. */
 int64_t sf_gma_stored_p_bytes(int n_img, int P);
 int sf_gma_flash_store_p(void* ws, int64_t ws_bytes, void* pbuf, int64_t pbuf_bytes, int n_img, int P, int qk_products,
                          void* stream);
@@ -551,7 +563,14 @@ int sf_flow_update(float* coords1, const float* delta, float* flow_a, int64_t fl
  *     qkv sf_gemm's c_f16 = 2 output; image stride in halves) instead of fp32 planes.
  *     Both *_mfma cores: out_koct (optional) = the result as fp16 k-octet planes [C/8][N][8] (SF_LAYOUT_F16_KOCT, image
  *     stride in halves): the B operand image of the proj sf_gemm that consumes it; out may then be NULL.
- * sf_dwconv3x3_res: timm PosConv: y = x + depthwise3x3(x) + b on [n_img][C][H][W]; w [C][9]. */
+ * sf_dwconv3x3_res: timm PosConv: y = x + depthwise3x3(x) + b on [n_img][C][H][W]; w [C][9].
+ * Established by tests/test_gpu_attn_kernels.py (ws 2..7, grids from 1 x 1, N and M on either side of 32 / 64 / 128 / 256):
+ *   sf_window_attn: heads must be a multiple of 4 (as for sf_window_attn_mfma), out may not be NULL; writes the H*W tokens of out only.
+ *   sf_window_attn_mfma: out alone, out_koct alone and both give bitwise the same values (out_koct = fp16(out));
+ *       SF_PRECISION_F16X2 and SF_PRECISION_F16 are bitwise the same; qkv_koct = 1 rounds the bias tokens' k and v to fp16.
+ *   sf_subsample_attn_ws_bytes: exactly that many bytes suffice; sf_subsample_attn_mfma writes nothing else outside its outputs.
+ *   sf_subsample_attn_mfma: the output requests and the two one-product classes agree bitwise as for sf_window_attn_mfma.
+ *   All four: image z of a batch is bitwise the call on image z alone, whatever the image strides. */
 int sf_window_attn(const float* qkv, int64_t qkv_img_stride, const float* qkv_bias, float* out, int64_t out_img_stride,
                    int n_img, int C, int heads, int H, int W, int ws, void* stream);
 int sf_window_attn_mfma(const void* qkv, int64_t qkv_img_stride, int qkv_koct, const float* qkv_bias, float* out,

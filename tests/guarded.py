@@ -1,7 +1,8 @@
 """Guard-banded device buffers for the descriptor tests (tests/test_gpu_gemm_descriptors.py, tests/test_gpu_chain_descriptors.py):
 a logical [batch][rows][cols] view placed inside a larger flat allocation -- leading dimension beyond the extent, a gap between
 images, a base off the allocation's start -- whose every other element holds a known fill (NaN for operands: a read that reaches a
-result shows; a finite sentinel for outputs) and must come back bitwise unchanged."""
+result shows; a finite sentinel for outputs) and must come back bitwise unchanged.  GuardedBytes: a byte workspace of exactly the
+size an entry point asks for, between two guard bands (tests/test_gpu_attn_kernels.py)."""
 import numpy as np
 import torch
 
@@ -57,6 +58,27 @@ class Guarded:
         a, b = self.buf[~self.inside], ref[~self.inside]
         return bool(torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a.view(torch.int16),
                                 b.view(torch.int32) if b.dtype == torch.float32 else b.view(torch.int16)))
+
+
+class GuardedBytes:
+    """A byte workspace of exactly `size` bytes between two guard bands of `guard` bytes (a multiple of `align`, so the workspace keeps
+    the allocation's alignment; shift > 0 moves it off that alignment).  The workspace is filled with `fill`, the bands with `band`;
+    guards_unchanged(): both bands are bitwise what they were."""
+
+    def __init__(self, dev, size, fill=0x7F, band=0xA5, guard=4096, shift=0):
+        self.size, self.guard, self.band = int(size), guard + shift, band
+        self.buf = torch.full((self.guard + self.size + guard,), band, dtype=torch.uint8, device=dev)
+        self.view().fill_(fill)
+
+    def view(self):
+        return self.buf[self.guard: self.guard + self.size]
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr() + self.guard
+
+    def guards_unchanged(self):
+        return bool((self.buf[: self.guard] == self.band).all()) and bool((self.buf[self.guard + self.size:] == self.band).all())
 
 
 def _operand(dev, rng, t, unaligned, dtype=torch.float32):
