@@ -94,7 +94,26 @@ int sf_corr_build_pyramid_pitched(const float* f1, const float* f2, int64_t f_cl
  * with -- SF_PRECISION_F16 means lvl0..lvl3 hold fp16 cells (taps are blended in fp32), anything else fp32 cells.
  * out_koct (optional, fp16 volumes only): the same 324 channels a second time, rounded to fp16, as k-octet planes
  * [41][h*w][8] per image (SF_LAYOUT_F16_KOCT, image stride out_koct_img_stride halves, rows 324..327 zero): the
- * B operand of the first sf_gemm of the correlation encoder. */
+ * B operand of the first sf_gemm of the correlation encoder.
+ * Established by tests/test_gpu_corr_kernels.py (grids 8 x 8 .. 24 x 40, D = 1 .. 256, B x pairs up to 2 x 2 and 1 x 3, every base,
+ * stride and pitch below with gaps and off 16 bytes):
+ *   sf_corr_build_ws_bytes = 2 * B * pairs * (D rounded up to 32) * h * w * 4; exactly that many bytes suffice, 16-byte aligned; the
+ *       SF_PRECISION_F16 build needs the same workspace as F16X3, SF_PRECISION_FP32 none.
+ *   builds write the data cells of the four levels -- with a pitch, the (h>>l) * lvl_pitch[l] cells of every map, pad cells included --
+ *       and nothing else: no cell between two pairs' spans, before the first or behind the last; f1, f2 are read only.
+ *   alignment: f1, f2, the level bases and `out` need their element's alignment only (4 bytes; 4 bytes for fp16 cells too, as the
+ *       parameters are float*); f_clip_stride, f_pair_stride, lvl_pair_stride (odd numbers of fp16 cells included), out_img_stride are
+ *       free.  An odd lvl_pair_stride in fp16 cells puts the packed 4-byte level-0 stores of the odd pairs on 2-byte aligned
+ *       addresses: the kernel has NO branch for that, the rule rests on gfx950 executing unaligned dword buffer stores (measured,
+ *       bitwise equal); code that assumes 4-byte alignment there must refuse odd strides first.
+ *       Aligned / vector and unaligned / scalar forms are bitwise the same: a placed run equals the contiguous one, pitched
+ *       data cells equal the dense ones, f2 in a buffer of its own equals f2 = f1 + f_pair_stride.
+ *   image (b, t) of a batch is bitwise the call on that pair alone (B = pairs = 1), builds and lookups.
+ *   F16X3 splits with streamflow_amd/csrc/split_operand.h split8(): towards zero twice, |x - (hi + lo)| < max(2^-20 |x|, 2^-24), 2^-23 for
+ *       |x| < 2^-14 -- not the round-to-nearest split of sf_gemm's ~2^-22; cells stay within the per-cell bound of tests/corr_cases.py.
+ *   lookups: a coordinate that is NaN, +-inf or, after the division by 2^l, not strictly inside (-1e6, 1e6) samples zero at that
+ *       level; the output is finite everywhere and exactly zero where all four taps lie outside the level (a 1 x 1 level included);
+ *       -0.0 is 0.  Beside fp32 planes out_koct is bitwise fp16(out) of the same launch, rows 324..327 zero; nothing else is written. */
 int sf_corr_lookup(const float* lvl0, const float* lvl1, const float* lvl2, const float* lvl3,
                    const int64_t* lvl_pair_stride, const float* coords, float* out, int64_t out_img_stride,
                    void* out_koct, int64_t out_koct_img_stride, int B, int pairs, int h, int w, int num_levels,
@@ -121,7 +140,20 @@ int sf_corr_lookup_pitched(const float* lvl0, const float* lvl1, const float* lv
  *   sf_corr_lookup_blocked: coords / channel order / sampling rule exactly as sf_corr_lookup.  out_koct: the 324 channels
  *       rounded to fp16 as k-octet planes [41][h*w][8] per image (SF_LAYOUT_F16_KOCT, rows 324..327 zero) -- the operand
  *       (and, through SfGemm.r_f16, the residual) of the correlation encoder's first block: no fp32 copy is written.
- *       out: optional fp32 planes [324][h*w] per image (un-rounded taps; API parity and tests).  At least one of the two. */
+ *       out: optional fp32 planes [324][h*w] per image (un-rounded taps; API parity and tests).  At least one of the two.
+ * Established by tests/test_gpu_corr_kernels.py (the same grids, depths and batches):
+ *   sf_corr_blocked_bytes = n_img * src_rows * rec_bytes and sf_corr_build_blocked_ws_bytes = 2 * n_img * 32 * Np * 16 with
+ *       Np = h*w + 1 rounded up to 8 (whatever D): exactly that many bytes suffice.  The build writes the src_rows * rec_bytes of every
+ *       image (padding cells and records included) and nothing between or behind the images; features are read only.
+ *   alignment: the build needs vol % 128 == 0 and a stride % 128 == 0 of at least sf_corr_blocked_bytes(1, h, w); the LOOKUP needs 16
+ *       bytes for vol and its stride only (a built volume may be moved); f1, f2, coords, out need 4 bytes, out_koct 16 and a stride % 8.
+ *   every frame is packed ONCE for both sides iff pairs > 1, f2 == f1 + f_pair_stride and 1 / sqrt(D) is not a power of two unless its
+ *       root is one too (D = 16, 256: sqrt(scale) folded into every frame; D = 64: packed per side, scale folded into f1).  With the
+ *       same folded factors the volume is bitwise the same whichever way f2 is handed over, and image (b, t) of a batch is bitwise the
+ *       call on that pair alone; with different ones (D = 16, 256) the two agree within the rounding of fp16 subnormal features.
+ *   placed runs (vol_img_stride_bytes, feature strides and bases, out / out_koct strides and bases) are bitwise the contiguous one.
+ *   lookup: non-finite and far coordinates as sf_corr_lookup; out alone, out_koct alone and both give bitwise the same values
+ *       (out_koct = fp16(out), rows 324..327 zero). */
 int sf_corr_blocked_geometry(int h, int w, int64_t* rec_bytes, int64_t* lvl_off, int32_t* nby, int32_t* nbx,
                              int64_t* src_rows);
 int64_t sf_corr_blocked_bytes(int n_img, int h, int w);
@@ -140,7 +172,15 @@ int sf_corr_lookup_blocked(const void* vol, int64_t vol_img_stride_bytes, const 
  * nbx = ceil(wl/8)), block (by, bx) at lvl_off[l] + (by*nbx[l] + bx)*128, cell (ty, tx) at byte ((tx%8)*4 + ty%4)*4 of block
  * (ty/4, tx/8).  A footprint touches ~6.9 cache lines per level instead of ~11.6 in the pitched row-major maps.
  * Padding cells / records: unspecified contents, never read.
- *   sf_corr_lookup_blocked32: out = fp32 planes [324][h*w] per image (channel order / sampling rule of sf_corr_lookup). */
+ *   sf_corr_lookup_blocked32: out = fp32 planes [324][h*w] per image (channel order / sampling rule of sf_corr_lookup).
+ * Established by tests/test_gpu_corr_kernels.py (the same grids, depths and batches):
+ *   sf_corr_blocked32_bytes = n_img * src_rows * rec_bytes; sf_corr_build_blocked32_ws_bytes = 2 * n_img * 2 * (D rounded up to 32) / 8
+ *       * h * w * 16 (= sf_corr_build_ws_bytes): exactly that many bytes suffice; the build writes the images' src_rows * rec_bytes only.
+ *   alignment as for the blocked fp16 volume (128 bytes for the build, 16 for the lookup, 4 for features, coords and out); frames
+ *       shared or f2 in a buffer of its own, placed or contiguous, batch or single pair: bitwise the same cells and features.
+ *   for unit-normal features (cells of O(1), D up to 256) cells agree with the pitched F16X3 build within 2e-6 and looked-up features
+ *       within 2e-5 (the same split8() operands, another summation order); the limits scale with the square of the feature scale;
+ *       non-finite and far coordinates as sf_corr_lookup. */
 int sf_corr_blocked32_geometry(int h, int w, int64_t* rec_bytes, int64_t* lvl_off, int32_t* nby, int32_t* nbx,
                                int64_t* src_rows);
 int64_t sf_corr_blocked32_bytes(int n_img, int h, int w);
