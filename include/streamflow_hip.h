@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 126
+#define SF_VERSION 127
 
 enum {
     SF_OK = 0,
@@ -522,10 +522,42 @@ int sf_softmax_rows(float* x, int64_t rows, int cols, void* out_f16, void* strea
  * Toeplitz GEMM on the matrix cores with fp32 accumulation.  SF_PRECISION_F16X3: (hi, lo) fp16 halves of both
  * operands, three products.  SF_PRECISION_F16X2: sf_gemm's f16x2 arithmetic -- weights hi + lo, the activation
  * enters the products rounded to fp16 (two products).  SF_PRECISION_F16: the weights are rounded once to fp16 as well (one
- * product; a single-product layer of the mixed preset).  The residual x stays exact in every mode.
+ * product; a single-product layer of the mixed preset).  The residual x is exact in the stencil and where x arrives as fp16
+ * rows through registers; on the matrix cores it is read back from the staged halves: hi + lo of the truncating split in
+ * SF_PRECISION_F16X3 (|x - (hi + lo)| <= 2^-20 |x|, as the correlation builds), hi + lo of the round-to-nearest split in the
+ * two- and one-product forms on fp32 input (2^-22 |x|); the DMA form of sf_dwconv_res_gelu_f16in at two products has no
+ * separate residual, its centre tap is the split of fp32(w_centre + 1).
  * y_f16 = 1: y receives IEEE fp16 planes of the same [img][c][h][w] order, y_img_stride counted in halves -- the
  * hand-over to a GEMM that reads them as SF_LAYOUT_F16_K_MAJOR (the engine's pw layer in the f16x2 mode, whose
- * residual is folded into its weights so that x3 has no other reader). */
+ * residual is folded into its weights so that x3 has no other reader).
+ *
+ * Established by tests/test_gpu_dwconv_kernels.py (both entry points; tests/dwconv_cases.py restates the dispatch):
+ *   Shapes.  ksize 7 or 15, h * w < 2^30.  The stencil (SF_PRECISION_FP32, and SF_PRECISION_F16X3 at ksize 7) takes
+ *   w <= 880 (ksize 15) / w <= 1620 (ksize 7) at every h whose strips fit the launch grid: its strip is as tall as 512 threads
+ *   allow, shortened until rows plus halo fit 64 KB of LDS, and more than 65535 strips are refused (tested up to h = 1000).
+ *   The matrix-core kernel (every other combination) takes w up to 480 (ksize 15) / 704 (ksize 7) at h = 16, at most 65535
+ *   strips, and planes whose outputs span at most 2^31 - 1 bytes: it addresses a plane with 32-bit byte offsets.  With fp16
+ *   input the plane may also hold at most 2^30 bytes (the offset the DMA form uses for "outside the plane"; the rule is applied
+ *   to the register form as well).  Tested with up to 15 images and 640 channels; n_img * C (the stencil's grid) is not checked.
+ *   Anything else, a y_f16 other than 0 / 1, a precision outside the enum, null pointers and non-positive sizes are refused
+ *   with SF_ERR_BAD_ARG before anything is written.
+ *   Placement.  Any 4-byte (fp16: 2-byte) aligned base and any image stride that keeps the images apart.  Alignment only selects
+ *   the access width and never the values: 16-byte aligned rows (w % 4 == 0, x_img_stride % 4 == 0) are staged with 16-byte loads
+ *   by the matrix-core kernel, 16-byte (fp16: 8-byte) aligned rows of y are stored four at a time by the stencil, and both are
+ *   bitwise the element-wise run.  fp16 rows with w % 8 == 0, x_img_stride % 8 == 0 and a 16-byte aligned base take the DMA form
+ *   where two staged planes rounded up to 4 KB fit LDS; every such placement is bitwise the dense one.  The DMA form and the
+ *   register form differ within 2^-9 max|y| + 2.5e-5 (the fold of the residual into the centre tap).
+ *   Batches.  Image z of a batch is bitwise the call on image z alone, for every number of images per workgroup.
+ *   Operand range.  The split precisions hold x in fp16 halves: |x| must stay below the fp16 maximum (65504).  A NaN or +inf
+ *   at one pixel (y0, x0) of x, or in the two- and one-product forms a finite value beyond that range, changes outputs of that
+ *   plane only: in the stencil exactly the K x K footprint, on the matrix cores exactly rows y0 - K/2 .. y0 + K/2 of every
+ *   16-column tile whose 32-column window (columns 16 t - 8 .. 16 t + 23) holds x0 -- the window is multiplied by a band with
+ *   structural zeros, and 0 * inf = NaN.  (SF_PRECISION_F16X3 keeps 1e5 finite, its split truncates, and changes the footprint
+ *   alone.)  NO OUTPUT IS NaN in either kernel: both GELU forms clamp their argument with max / med3, which return the other
+ *   operand for a NaN, so a NaN or -inf pre-activation leaves as a number within the form's absolute error of zero, and +inf
+ *   as +inf.  A caller that needs to see non-finite input must check x itself.
+ *   GELU.  fp16 output of the two- and one-product forms uses the polynomial GELU of csrc/sf_common.h (5.2e-5 absolute up to
+ *   a pre-activation of 8, 6.6e-6 of it beyond); everything else the erf form (1.3e-6, 3e-7 of the pre-activation beyond 4). */
 int sf_dwconv_res_gelu(const float* x, int64_t x_img_stride, const float* wgt, const float* bias, void* y,
                        int64_t y_img_stride, int y_f16, int n_img, int C, int h, int w, int ksize, int precision,
                        void* stream);

@@ -14,6 +14,7 @@
 // lgkmcnt(0) drain -- and a register sliding window that cuts the LDS row reads 4x changed nothing: the
 // kernel is bound by VALU issue, 47 TFLOP/s of fp32 FMA.)
 #include "sf_common.h"
+#include <climits>
 #include <cstdlib>
 #include "split_operand.h"
 
@@ -480,6 +481,10 @@ static int dwconv_dispatch(const void* x_, int x_f16, int64_t x_img_stride, cons
                                          "SF_PRECISION_F16X2 or SF_PRECISION_F16)");
     // K = 7 in the two-product modes also runs on the matrix cores (7 x 2 MFMAs per tile against 49 FMAs per output)
     if (precision != SF_PRECISION_FP32 && (ksize == 15 || two)) {
+        // the kernel addresses a plane with 32-bit byte offsets and builds its buffer resources with `int` record counts; the DMA
+        // form marks "outside the plane" with the offset 2^30, which must lie beyond an fp16 input plane
+        SF_REQUIRE((int64_t)h * w * (y_f16 ? 2 : 4) <= INT32_MAX && (!x_f16 || (int64_t)h * w * 2 <= (1 << 30)),
+                   "sf_dwconv_res_gelu: a plane of %d x %d does not fit the matrix-core kernel's 32-bit byte offsets", h, w);
         DwmArgs m;
         m.x = x; m.wgt = wgt; m.bias = bias; m.y = y; m.x_img_stride = x_img_stride; m.y_img_stride = y_img_stride;
         m.n_img = n_img; m.C = C; m.h = h; m.w = w;
@@ -556,14 +561,17 @@ static int dwconv_dispatch(const void* x_, int x_f16, int64_t x_img_stride, cons
     SF_REQUIRE(g.tiles_x <= kMaxThreads, "sf_dwconv_res_gelu: width %d too large", w);
     int tiles_y = sf::ceil_div(h, TY);
     if (tiles_y * g.tiles_x > kMaxThreads) tiles_y = kMaxThreads / g.tiles_x;
-    g.strip_h = tiles_y * TY;
     g.wp4 = (g.tiles_x * TX + ksize - 1 + 3) / 4;
+    // the strip is as tall as the threads allow, then shortened until its rows plus halo fit LDS (a wide or a tall narrow plane)
+    auto lds_of = [&](int ty) { return ((size_t)(ty * TY + ksize - 1) * g.wp4 * 4 + 8 + ksize * ksize + 8) * sizeof(float); };
+    while (tiles_y > 1 && lds_of(tiles_y) > 64 * 1024) --tiles_y;
+    g.strip_h = tiles_y * TY;
     g.vec_store = ((w & 3) == 0) && ((y_img_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(y) & (y_f16 ? 7 : 15)) == 0);
-    const int rows = g.strip_h + ksize - 1;
-    const size_t lds = ((size_t)rows * g.wp4 * 4 + 8 + ksize * ksize + 8) * sizeof(float);
-    SF_REQUIRE(lds <= 64 * 1024, "sf_dwconv_res_gelu: strip needs %zu bytes of LDS", lds);
+    const size_t lds = lds_of(tiles_y);
+    SF_REQUIRE(lds <= 64 * 1024, "sf_dwconv_res_gelu: a strip of %d rows needs %zu bytes of LDS: width %d too large", g.strip_h, lds, w);
     const int threads = ((tiles_y * g.tiles_x + 63) / 64) * 64;
     dim3 grid(n_img * C, sf::ceil_div(h, g.strip_h));
+    SF_REQUIRE(grid.y <= 65535, "sf_dwconv_res_gelu: grid too large");
     if (ksize == 15 && y_f16)
         hipLaunchKernelGGL((dwconv_res_gelu_kernel<15, true>), grid, dim3(threads), lds, (hipStream_t)stream, g);
     else if (ksize == 15)
@@ -582,7 +590,8 @@ extern "C" int sf_dwconv_res_gelu(const float* x, int64_t x_img_stride, const fl
 }
 
 // x as fp16 ROWS [img][C][h*w] (x_img_stride in halves), y as fp16 rows: the config-2 hand-over of an SK block's x2 and x3
-// (precision SF_PRECISION_F16X2 or SF_PRECISION_F16).  The conv input and the residual are the fp16 value itself.
+// (precision SF_PRECISION_F16X2 or SF_PRECISION_F16).  The conv input is the fp16 value itself, and so is the residual, except in the
+// DMA form at two products: that one has no separate residual, its centre tap is the split of fp32(w_centre + 1) (kFoldRes).
 extern "C" int sf_dwconv_res_gelu_f16in(const void* x_f16, int64_t x_img_stride, const float* wgt, const float* bias,
                                         void* y_f16, int64_t y_img_stride, int n_img, int C, int h, int w, int ksize,
                                         int precision, void* stream) {

@@ -43,7 +43,8 @@ __device__ __forceinline__ float erf_fast(float x) {
 
 // exact (erf-based) GELU, as F.gelu / nn.GELU default: 0.5 x (1 + erf(x / sqrt(2)))
 // (x / 2 is clamped below where the erf argument saturates: 1 + erf_fast(-4) is 0 only to the fit's 4.5e-7, which times an
-// unbounded |x| / 2 would be an error growing with |x|; clamped it stays <= 1.3e-6 for every x)
+// unbounded |x| / 2 would be an error growing with |x|; clamped it stays <= 1.3e-6 for every x <= 4.  For larger x the fit's
+// error and the fp32 roundings of the two products are relative: 3e-7 x, restated and measured in tests/test_dwconv_cases_cpu.py)
 __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * fmaxf(x, -5.6568542f) * (1.0f + erf_fast(x * 0.70710678118654752440f));
 }
@@ -92,9 +93,11 @@ __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
 // output of the depthwise kernel): a pure polynomial -- erf(z) ~ z Q(z^2) on |z| <= 3 (degree-8 minimax
 // Q, |err| <= 2.2e-5, erf(3) = 1 - 2.2e-5 beyond), constants folded so that gelu(x) = h + h * (xc * D(xc^2)), h = x / 2,
 // xc = x clamped to +-3 sqrt 2: 14 issue slots per PAIR (2 v_med3, 10 v_pk_fma / v_pk_mul, no v_rcp) against 28 for the
-// rational form above.  |gelu error| <= 5.2e-5 absolute for EVERY x (h is clamped below at -3/sqrt 2, so that the residue of
-// erf(3) != 1 stays 4.7e-5 instead of growing like 1.1e-5 |x|: ADVICE r2) and <= 1.1e-5 relative for x > 0 -- a tenth of the
-// fp16 rounding (2^-11 relative) that every activation of these modes receives on its way into the next contraction.
+// rational form above.  |gelu error| <= 5.2e-5 absolute for every x <= 8 (h is clamped below at -3/sqrt 2, so that the residue of
+// erf(3) != 1 stays 4.7e-5 for negative x instead of growing like 1.1e-5 |x|: ADVICE r2).  Beyond the clamp of xc the error is that
+// residue times x / 2 and DOES grow: 6.6e-6 x, above 5.2e-5 from x = 8 on.  Relative to gelu(x) it is <= 1.35e-5 for x > 0 (1.2e-5
+// of x) -- a fortieth of the fp16 rounding (2^-11 relative) that every activation of these modes receives on its way into the next
+// contraction.  (Restated in float64 and in fp32 and measured on a grid over [-12, 12]: tests/test_dwconv_cases_cpu.py.)
 __device__ __forceinline__ f32x2 gelu_poly2(f32x2 x) {
     f32x2 xc;
     xc[0] = __builtin_amdgcn_fmed3f(x[0], -4.2426405f, 4.2426405f);
