@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 127
+#define SF_VERSION 128
 
 enum {
     SF_OK = 0,
@@ -813,6 +813,28 @@ int sf_frames_to_clips(const uint8_t* frames, int64_t frame_stride, int64_t row_
 int sf_clips_to_flows(const SfPairPtrs* pairs, int64_t clip_stride, int64_t ch_stride, int64_t row_stride, int n, int T,
                       int first_clip, int n_clips, int pair0, int n_pairs, int H, int W, int pad_top, int pad_left, float* out,
                       void* stream);
+
+/* ---- PNG frames: row unfiltering of inflated IDAT streams (PNG specification, section 9; flow_io.read_png on the host) ----------
+ * The host inflates (zlib); the device undoes the row filters of a whole batch of equally shaped images in one launch, so the
+ * decoded frames are born where sf_frames_to_clips and sf_flow_score_batch read them.
+ *
+ * sf_png_unfilter: scan + i scan_image_stride is the inflated IDAT stream of image i: h rows of 1 + w bpp bytes, dense, each with
+ *   its filter-type byte first (rows therefore start at arbitrary byte addresses; nothing is assumed about alignment).  bpp is the
+ *   PNG filter distance = bytes per pixel: 1, 2, 3, 4, 6 or 8 (8 / 16-bit grey, grey + alpha, RGB, RGBA).  The reconstructed byte x
+ *   of row y goes to out[i out_image_stride + y out_row_stride + x], with swap16 != 0 to ... + (x ^ 1) (16-bit samples in host
+ *   order; needs an even bpp).  Every byte of the h x (w bpp) view is written, nothing outside it.  Filter types 0 .. 4 = None, Sub,
+ *   Up, Average ((a + b) >> 1 on 9 bits), Paeth (ties a, b, c), all mod 256; a = c = 0 in the first bpp bytes of a row, b = c = 0 in
+ *   row 0.  A filter byte above 4 is treated as type 0 (flow_io.png_scanlines rejects such files before anything is uploaded).
+ *   One workgroup per image walks it in bands of SF_PNG_BAND_ROWS rows, a thread per row, one pixel per step along the
+ *   anti-diagonals; the row handed from band to band lives in LDS, hence SF_PNG_MAX_ROW_BYTES.  No data passes between workgroups
+ *   and every loop's trip count depends on (h, w) alone.  One launch, no host synchronisation.
+ *   SF_ERR_BAD_ARG before any launch for: null pointers, n_images outside 1 .. 65535, h or w < 1, a bpp outside the set above, swap16
+ *   with an odd bpp, scan_image_stride < h (1 + w bpp), out_row_stride < w bpp, out_image_stride < (h - 1) out_row_stride + w bpp,
+ *   h (1 + w bpp) >= 2^31.  SF_ERR_UNSUPPORTED for w bpp > SF_PNG_MAX_ROW_BYTES. */
+#define SF_PNG_BAND_ROWS 256
+#define SF_PNG_MAX_ROW_BYTES 40960 /* 5120 pixels of 16-bit RGBA; the kernel keeps one row of this size and 4 KiB more in LDS */
+int sf_png_unfilter(const uint8_t* scan, int64_t scan_image_stride, int n_images, int h, int w, int bpp, uint8_t* out,
+                    int64_t out_image_stride, int64_t out_row_stride, int swap16, void* stream);
 
 #ifdef __cplusplus
 }

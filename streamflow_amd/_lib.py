@@ -184,6 +184,7 @@ SIGNATURES = {
     "sf_flow_score_batch": (_i, [C.POINTER(SfScoreFields), _i, _i64, _i64, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "sf_frames_to_clips": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_clips_to_flows": (_i, [C.POINTER(SfPairPtrs), _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sf_png_unfilter": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -209,7 +210,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 127:
+    if lib.sf_version() < 128:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -100,15 +100,16 @@ def vis_flow(flows_result: Sequence[torch.Tensor], save_dir: str = "flow_result"
 
 
 def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, clips_per_step: int = 8, mode: str = "sintel",
-                                  save_dir: str = None, flo_dir: str = None, rad_max=None) -> int:
+                                  save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host") -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames: video.FrameDir ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
     are coloured on the GPU and written as ``save_dir/frame_%04d.png`` (numbered by pair) and, with `flo_dir`, as Middlebury
-    ``flo_dir/frame_%04d.flo``.  Runs on the current GPU.  Returns the number of pairs."""
+    ``flo_dir/frame_%04d.flo``.  png_decode="gpu": the frames' PNG rows are unfiltered on the GPU (video.FrameDir(decode="gpu")), the
+    same bytes as the host decoder's.  Runs on the current GPU.  Returns the number of pairs."""
     import os
     from . import flow_io, video
     from .model import StreamFlowT4
-    frames = video.FrameDir(path)
+    frames = video.FrameDir(path, decode=png_decode)
     if not torch.cuda.is_available():
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -145,10 +146,12 @@ def main(argv=None) -> int:
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--clips-per-step", type=int, default=8)
     ap.add_argument("--mode", default="sintel", choices=("sintel", "kitti"))
+    ap.add_argument("--png-decode", default="gpu", choices=("gpu", "host"),
+                    help="where the frames' PNG rows are unfiltered (the same bytes either way)")
     ap.add_argument("--rad-max", type=float, default=None, help="one colour scale for the whole video (default: per frame)")
     a = ap.parse_args(argv)
     n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
-                                      save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max)
+                                      save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode)
     print(f"{n} flow fields -> {a.out}" + (f", {a.flo}" if a.flo else ""))
     return 0
 

@@ -63,6 +63,11 @@ def _occlusion(path: str, hw: Tuple[int, int]) -> np.ndarray:
     return np.ascontiguousarray(m)
 
 
+def _check_png_decode(png_decode: str) -> None:
+    if png_decode not in ("host", "gpu"):
+        raise ValueError(f"png_decode {png_decode!r} ('host' or 'gpu')")
+
+
 def _need_gpu(what: str, dev: torch.device) -> torch.device:
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError(f"{what}: clips_per_step > 1 runs on the GPU (device {dev}, GPU available: {torch.cuda.is_available()}); "
@@ -73,7 +78,7 @@ def _need_gpu(what: str, dev: torch.device) -> torch.device:
 @torch.no_grad()
 def sintel_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", nframes: int = 3,
                   dstypes: Sequence[str] = ("clean", "final"), device: Optional[torch.device] = None, clips_per_step: int = 1,
-                  occ: bool = False) -> Dict[str, Dict[str, float]]:
+                  occ: bool = False, png_decode: str = "host") -> Dict[str, Dict[str, float]]:
     """Per render pass: {'epe', '1px', '3px', '5px', 'pairs'} over every scored pair of every scene.  clips_per_step > 1: that many
     clips per model call, scored on the GPU (adds 'pixels'); occ: also 'epe_occ', 'epe_noc', 'occ_pixels' from the scenes'
     occlusion maps.
@@ -83,8 +88,11 @@ def sintel_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
     through the EVAL accumulator (scoring.py), one row per scored pair: device flows by ops.flow_score_batch, host flows (a CPU
     model) by scoring.score_host_fields with the same arithmetic; the device rows are copied to the host once, at the end of the
     report.  clips_per_step > 1: per scene, the uint8 frames (each decoded once) go through video.predict_video and every batch's
-    flows are scored as they arrive (its `sink`), so neither a flow nor a whole scene's flows leave the GPU or stay on it."""
-    from . import ops, scoring, video
+    flows are scored as they arrive (its `sink`), so neither a flow nor a whole scene's flows leave the GPU or stay on it.
+    png_decode="gpu" (with clips_per_step > 1): a scene's frames are inflated on the host and unfiltered on the GPU
+    (png_gpu.decode_frames) and reach predict_video as one device tensor; the same bytes, so the same report."""
+    from . import ops, png_gpu, scoring, video
+    _check_png_decode(png_decode)
     dev = device or model_device(model, torch.device("cpu"))
     clips_per_step, occ = int(clips_per_step), bool(occ)
     per_pixel = clips_per_step == 1 and not occ
@@ -110,8 +118,9 @@ def sintel_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
                     m = None if masks is None else list(torch.from_numpy(np.stack(masks)).to(flows.device))
                     ops.flow_score_batch(list(flows), list(g), acc[first_pair:first_pair + flows.shape[0]], "flo", m)
 
-                video.predict_video(model, [read_frame(p) for p in imgs], T=nframes, iters=iters, clips_per_step=clips_per_step,
-                                    mode="sintel", device=dev, sink=score)
+                frames = png_gpu.decode_frames(imgs, dev) if png_decode == "gpu" else [read_frame(p) for p in imgs]
+                video.predict_video(model, frames, T=nframes, iters=iters, clips_per_step=clips_per_step, mode="sintel", device=dev,
+                                    sink=score)
                 rows[dstype].append(acc)
                 continue
             for first, ids in sintel_clip_schedule(len(imgs), nframes):
@@ -163,35 +172,37 @@ def sintel_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
 
 @torch.no_grad()
 def validate_sintel_mf(model: Callable, iters: int = 6, root: str = "/data/Sintel", tqdm_miniters: int = 1, nframes: int = 3,
-                       device: Optional[torch.device] = None, clips_per_step: int = 1) -> Dict[str, float]:
+                       device: Optional[torch.device] = None, clips_per_step: int = 1, png_decode: str = "host") -> Dict[str, float]:
     """The reference's return value: {'clean': mean EPE, 'final': mean EPE}  (evaluate_mf.py:468-503)."""
-    return {k: v["epe"] for k, v in sintel_report(model, iters, root, nframes, device=device,
-                                                  clips_per_step=clips_per_step).items()}
+    return {k: v["epe"] for k, v in sintel_report(model, iters, root, nframes, device=device, clips_per_step=clips_per_step,
+                                                  png_decode=png_decode).items()}
 
 
 @torch.no_grad()
 def validate_sintel_occ_mf(model: Callable, iters: int = 6, root: str = "/data/Sintel", tqdm_miniters: int = 1, nframes: int = 3,
-                           clips_per_step: int = 1, device: Optional[torch.device] = None) -> Dict[str, float]:
+                           clips_per_step: int = 1, device: Optional[torch.device] = None, png_decode: str = "host") -> Dict[str, float]:
     """The reference's validate_sintel_occ_mf (evaluate_mf.py:549-592): the passes albedo, clean and final, per pass the line of
     validate_sintel_mf and "Occ epe: .., Noc epe: .."; returns {pass: mean EPE}.  `tqdm_miniters` is accepted and ignored."""
     if hasattr(model, "eval"):
         model.eval()
     rep = sintel_report(model, iters, root, nframes, dstypes=("albedo", "clean", "final"), device=device,
-                        clips_per_step=clips_per_step, occ=True)
+                        clips_per_step=clips_per_step, occ=True, png_decode=png_decode)
     return {k: v["epe"] for k, v in rep.items()}
 
 
 @torch.no_grad()
 def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str] = None, nframes: int = 3,
-                      device: Optional[torch.device] = None, clips_per_step: int = 1) -> Dict[str, float]:
+                      device: Optional[torch.device] = None, clips_per_step: int = 1, png_decode: str = "host") -> Dict[str, float]:
     """{'kitti_epe', 'kitti_f1'} over the sequences present under multi_root/training (the reference walks 000000 .. 000199).
-    clips_per_step > 1: up to that many sequences of one frame size per model call, scored on the GPU (_kitti_batched)."""
+    clips_per_step > 1: up to that many sequences of one frame size per model call, scored on the GPU (_kitti_batched); with
+    png_decode="gpu" their frames and flow_occ files are unfiltered on the GPU too."""
+    _check_png_decode(png_decode)
     if multi_root is None:
         raise ValueError("validate_kitti_mf: multi_root (the multi-frame KITTI-2015 tree) is required")
     dev = device or model_device(model, torch.device("cpu"))
     image_root, flow_root, seqs = kitti_mf_sequences(multi_root, "training")
     if int(clips_per_step) != 1:
-        return _kitti_batched(model, iters, image_root, flow_root, seqs, nframes, dev, int(clips_per_step))
+        return _kitti_batched(model, iters, image_root, flow_root, seqs, nframes, dev, int(clips_per_step), png_decode)
 
     def pairs():
         for seq in seqs:
@@ -205,13 +216,17 @@ def validate_kitti_mf(model: Callable, iters: int = 6, multi_root: Optional[str]
 
 
 def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str, seqs: Sequence[str], nframes: int,
-                   dev: torch.device, clips_per_step: int) -> Dict[str, float]:
+                   dev: torch.device, clips_per_step: int, png_decode: str = "host") -> Dict[str, float]:
     """validate_kitti_mf, `clips_per_step` sequences per model call: consecutive sequences whose frames have one size (KITTI has
     five widths) are collected, each one's uint8 frames become a clip by ops.frames_to_clips (a video of n = T frames, 'kitti'
     padding), the clips run as one batch, and the last pair of every clip is scored in one ops.flow_score_batch call against the
     16-bit PNG samples as read (decoded in the kernel).  A size change and the end of the list flush the batch.  One accumulator
-    row per sequence; scoring.kitti_from forms the reference's mean of per-image means and the F1-all rate."""
-    from . import ops, scoring
+    row per sequence; scoring.kitti_from forms the reference's mean of per-image means and the F1-all rate.
+    png_decode="gpu": a batch's frame files and its flow_occ files are inflated on the host and unfiltered on the GPU when the
+    batch is flushed (png_gpu: one launch for the frames, one for the ground truth); the scoring call takes the decoded uint16
+    samples where they are, nothing is uploaded but the scanlines."""
+    from . import ops, png_gpu, scoring, video
+    _check_png_decode(png_decode)
     if clips_per_step < 1:
         raise ValueError(f"clips_per_step must be at least 1, got {clips_per_step}")
     dev = _need_gpu("validate_kitti_mf", dev)
@@ -223,9 +238,22 @@ def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str,
         if not pending:
             return
         k = len(pending)
-        H, W = pending[0][0].shape[1:3]
+        if png_decode == "gpu":                                          # pending: (frame files, flow_occ file, (H, W))
+            H, W = pending[0][2]
+            frames = png_gpu.decode_frames([p for clip, _, _ in pending for p in clip], dev).view(k, T, H, W, 3)
+            smp = png_gpu.decode_batch([g for _, g, _ in pending], dev)
+            if smp.dtype == torch.uint8 or smp.shape[3] < 3:
+                raise IOError(f"{pending[0][1]}: KITTI flow needs a 16-bit RGB PNG, got {smp.dtype} {tuple(smp.shape[1:])}")
+            if tuple(smp.shape[1:3]) != (H, W):
+                raise RuntimeError(f"{pending[0][1]}: ground truth {tuple(smp.shape[1:3])} for frames {(H, W)}")
+            # (as int16, the same bits: the dtype the host path hands over, and one every torch build can slice and copy)
+            gts = smp.view(torch.int16)[..., :3].contiguous()
+        else:
+            H, W = pending[0][0].shape[1:3]
+            frames = torch.from_numpy(np.stack([f for f, _ in pending])).to(dev)
+            # (the 16-bit samples travel as int16: the same bits, a dtype every torch build can copy to the device)
+            gts = torch.from_numpy(np.stack([g for _, g in pending]).view(np.int16)).to(dev)
         pad = InputPadder((H, W), mode="kitti")._pad                     # [left, right, top, bottom]
-        frames = torch.from_numpy(np.stack([f for f, _ in pending])).to(dev)
         clips = torch.empty(k, T, 3, H + pad[2] + pad[3], W + pad[0] + pad[1], dtype=torch.float32, device=dev)
         for i in range(k):
             ops.frames_to_clips(frames[i], T, T, 0, 1, pad, channels_last=True, out=clips[i:i + 1])
@@ -234,8 +262,6 @@ def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str,
             raise RuntimeError(f"validate_kitti_mf: the model returned {len(flows)} flows for clips of T = {T}")
         last = flows[T - 2].float()                                      # only the last pair (frames 10 -> 11) has ground truth
         preds = [last[i][:, pad[2]:pad[2] + H, pad[0]:pad[0] + W] for i in range(k)]
-        # (the 16-bit samples travel as int16: the same bits, a dtype every torch build can copy to the device)
-        gts = torch.from_numpy(np.stack([g for _, g in pending]).view(np.int16)).to(dev)
         acc = torch.zeros(k, scoring.EVAL_LEN, dtype=torch.float64, device=dev)
         ops.flow_score_batch(preds, list(gts), acc, "kitti")
         rows.append(acc)
@@ -243,8 +269,15 @@ def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str,
 
     with torch.cuda.device(dev):
         for seq in seqs:
-            frames = np.stack([read_frame(p) for p in kitti_mf_clip(image_root, seq, T)])
             path = os.path.join(flow_root, seq + "_10.png")
+            if png_decode == "gpu":                                      # only the headers now: the files are read at the flush
+                clip = kitti_mf_clip(image_root, seq, T)
+                hw = video._png_size(clip[0])
+                if pending and (len(pending) == clips_per_step or pending[0][2] != hw):
+                    flush()
+                pending.append((clip, path, hw))
+                continue
+            frames = np.stack([read_frame(p) for p in kitti_mf_clip(image_root, seq, T)])
             smp = flow_io.read_png(path)
             if smp.ndim != 3 or smp.shape[2] < 3 or smp.dtype != np.uint16:
                 raise IOError(f"{path}: KITTI flow needs a 16-bit RGB PNG, got {smp.dtype} {smp.shape}")
@@ -445,15 +478,19 @@ def main(argv=None) -> int:
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--clips-per-step", type=int, default=8,
                     help="clips per model call (sintel, sintel_occ, kitti; 1 = the reference's per-clip loop scored on the host)")
+    ap.add_argument("--png-decode", default="gpu", choices=("gpu", "host"),
+                    help="where PNG rows are unfiltered when clips-per-step > 1 (the same bytes either way; 1 always decodes on the host)")
     ap.add_argument("--preset", default=None, help="arithmetic preset (streamflow_amd.presets); default: fp32_class")
     a = ap.parse_args(argv)
+    png_decode = a.png_decode if a.clips_per_step > 1 else "host"
     model = load_model(a.ckpt, T=a.T, preset=a.preset)
     if a.dataset == "sintel":
-        res = validate_sintel_mf(model, iters=a.iters, root=a.root, nframes=a.T, clips_per_step=a.clips_per_step)
+        res = validate_sintel_mf(model, iters=a.iters, root=a.root, nframes=a.T, clips_per_step=a.clips_per_step, png_decode=png_decode)
     elif a.dataset == "sintel_occ":
-        res = validate_sintel_occ_mf(model, iters=a.iters, root=a.root, nframes=a.T, clips_per_step=a.clips_per_step)
+        res = validate_sintel_occ_mf(model, iters=a.iters, root=a.root, nframes=a.T, clips_per_step=a.clips_per_step,
+                                     png_decode=png_decode)
     elif a.dataset == "kitti":
-        res = validate_kitti_mf(model, iters=a.iters, multi_root=a.root, nframes=a.T, clips_per_step=a.clips_per_step)
+        res = validate_kitti_mf(model, iters=a.iters, multi_root=a.root, nframes=a.T, clips_per_step=a.clips_per_step, png_decode=png_decode)
     elif a.dataset == "kitti_tile":
         res = validate_kitti_mf_tile(model, iters=a.iters, multi_root=a.root, nframes=a.T)
     else:

@@ -117,8 +117,11 @@ def write_png(path: str, img: np.ndarray) -> None:
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
-def read_png(path: str) -> np.ndarray:
-    """Non-interlaced 8/16-bit gray / gray+alpha / RGB / RGBA PNG -> uint8 / uint16 [H, W, C] (C squeezed when 1)."""
+def png_scanlines(path: str) -> Tuple[np.ndarray, int, int, int, int]:
+    """The inflated IDAT stream of a non-interlaced 8/16-bit gray / gray+alpha / RGB / RGBA PNG, still filtered:
+    (raw uint8 [h * (1 + w * bpp)], h, w, bit depth, channels), bpp = channels * depth / 8.  Row y is raw[y * (1 + w * bpp):][:1 + w * bpp],
+    its filter-type byte (0 .. 4) first.  The chunk walk, the CRC and header checks and the inflate of read_png; the unfilter is
+    read_png's (host) or ops.png_unfilter's (GPU: png_gpu.decode_batch)."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:8] != _PNG_SIG:
@@ -144,11 +147,21 @@ def read_png(path: str) -> np.ndarray:
     if depth not in (8, 16) or ctype not in _PNG_CHANNELS or interlace:
         raise IOError(f"{path}: unsupported PNG (bit depth {depth}, colour type {ctype}, interlace {interlace})")
     c = _PNG_CHANNELS[ctype]
-    bpp = c * depth // 8                                   # bytes per pixel = filter distance
-    stride = w * bpp
+    stride = w * c * depth // 8
     raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
     if raw.size != h * (stride + 1):
         raise IOError(f"{path}: truncated image data")
+    if raw.size and int(raw[::stride + 1].max()) > 4:
+        ft = raw[::stride + 1]
+        raise IOError(f"{path}: bad filter type {int(ft[ft > 4][0])}")
+    return raw, h, w, depth, c
+
+
+def read_png(path: str) -> np.ndarray:
+    """Non-interlaced 8/16-bit gray / gray+alpha / RGB / RGBA PNG -> uint8 / uint16 [H, W, C] (C squeezed when 1)."""
+    raw, h, w, depth, c = png_scanlines(path)
+    bpp = c * depth // 8                                   # bytes per pixel = filter distance
+    stride = w * bpp
     raw = raw.reshape(h, stride + 1)
     out = np.zeros((h, stride), np.uint8)
     prev = np.zeros(stride, np.uint8)

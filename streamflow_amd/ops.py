@@ -1440,6 +1440,43 @@ def clips_to_flows(pairs: Sequence[torch.Tensor], n: int, T: int, first_clip: in
     return out
 
 
+PNG_BPP = (1, 2, 3, 4, 6, 8)          # PNG filter distances sf_png_unfilter is built for: 8 / 16-bit grey, grey + alpha, RGB, RGBA
+
+
+@on_tensor_device
+def png_unfilter(scan: torch.Tensor, h: int, w: int, bpp: int, out: Optional[torch.Tensor] = None, swap16: bool = False) -> torch.Tensor:
+    """Undo the PNG row filters of a batch of inflated IDAT streams (sf_png_unfilter, one launch; the host side of it is
+    flow_io.png_scanlines): scan uint8 [n, h * (1 + w * bpp)] on the GPU, rows contiguous (any row stride), image i's h scanlines
+    with their filter-type bytes; bpp the filter distance (PNG_BPP).  Returns (or fills `out`: uint8 [n, h, w * bpp] on the same
+    GPU with contiguous bytes in a row, any row / image strides) the reconstructed bytes; swap16 swaps the bytes of every 16-bit
+    sample, so `.view(torch.uint16)` of a contiguous result holds the samples in host order.  Enqueued on the current stream, no
+    synchronisation."""
+    if not isinstance(scan, torch.Tensor) or not scan.is_cuda:
+        raise RuntimeError(f"png_unfilter: scan must be on the GPU (got {getattr(scan, 'device', type(scan).__name__)}); "
+                           "there is no CPU fallback -- flow_io.read_png is the host-side path")
+    h, w, bpp = int(h), int(w), int(bpp)
+    if bpp not in PNG_BPP or h < 1 or w < 1:
+        raise RuntimeError(f"png_unfilter: h = {h}, w = {w}, bpp = {bpp} (bpp one of {PNG_BPP})")
+    if scan.dtype != torch.uint8 or scan.dim() != 2 or scan.shape[0] < 1 or scan.shape[1] != h * (1 + w * bpp) or scan.stride(1) != 1:
+        raise RuntimeError(f"png_unfilter: scan must be uint8 [n, {h * (1 + w * bpp)}] with contiguous rows (got {scan.dtype} "
+                           f"{tuple(scan.shape)}, strides {scan.stride()})")
+    if swap16 and bpp % 2:
+        raise RuntimeError(f"png_unfilter: swap16 needs an even bpp (got {bpp})")
+    n = int(scan.shape[0])
+    shape = (n, h, w * bpp)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=scan.device)
+    elif (tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != scan.device or out.stride(2) != 1
+          or out.stride(1) < w * bpp or (n > 1 and out.stride(0) < (h - 1) * out.stride(1) + w * bpp)):
+        raise RuntimeError(f"png_unfilter: out must be uint8 {shape} on {scan.device} with contiguous bytes in a row and "
+                           f"non-overlapping rows and images (got {out.dtype} {tuple(out.shape)} on {out.device}, strides {out.stride()})")
+    scan_stride = scan.stride(0) if n > 1 else h * (1 + w * bpp)
+    out_stride = out.stride(0) if n > 1 else (h - 1) * out.stride(1) + w * bpp
+    _lib.check(_lib.load().sf_png_unfilter(scan.data_ptr(), scan_stride, n, h, w, bpp, out.data_ptr(), out_stride, out.stride(1),
+                                           1 if swap16 else 0, _lib.stream()), "sf_png_unfilter")
+    return out
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None

@@ -74,9 +74,17 @@ def _png_size(path: str) -> Tuple[int, int]:
 class FrameDir:
     """The PNG frames of a directory, sorted by name, as a lazy sequence of uint8 [H, W, 3] arrays: a frame is decoded
     (datasets.read_frame: grey replicated to three channels, alpha dropped) when it is indexed and not kept.  All frames must have
-    one size: the headers are compared when the object is made, the decoded arrays again when they are read."""
+    one size: the headers are compared when the object is made, the decoded arrays again when they are read.
 
-    def __init__(self, path: str, pattern: str = "*.png"):
+    decode="gpu": predict_video takes a batch's frames through `device_batch` -- inflated on the host, unfiltered on the device
+    (png_gpu.decode_frames), the same bytes -- instead of indexing them one by one; indexing a single frame still decodes on the
+    host.  The default "host" is the path above alone."""
+
+    def __init__(self, path: str, pattern: str = "*.png", decode: str = "host"):
+        if decode not in ("host", "gpu"):
+            raise ValueError(f"FrameDir: decode {decode!r} ('host' or 'gpu')")
+        if decode == "gpu":
+            self.device_batch = self._device_batch                       # (_Source looks for the attribute)
         self.paths = sorted(glob.glob(os.path.join(path, pattern)))
         if not self.paths:
             raise FileNotFoundError(f"no frames matching {pattern!r} in {path}")
@@ -95,6 +103,14 @@ class FrameDir:
         if img.shape[:2] != self.hw:
             raise ValueError(f"{self.paths[i]}: frame size {img.shape[:2]} differs from {self.hw}")
         return img
+
+    def _device_batch(self, lo: int, hi: int, dev: torch.device) -> torch.Tensor:
+        """The frames lo .. hi - 1 as uint8 [hi - lo, H, W, 3] on `dev`; raises without a GPU (no fallback to the host decoder)."""
+        from . import png_gpu
+        out = png_gpu.decode_frames(self.paths[lo:hi], dev)
+        if tuple(out.shape[1:3]) != self.hw:
+            raise ValueError(f"{self.paths[lo]}: frame size {tuple(out.shape[1:3])} differs from {self.hw}")
+        return out
 
 
 class _Source:
@@ -150,6 +166,8 @@ class _Source:
                     raise RuntimeError(f"predict_video: frames on {self.stack.device}, model on {dev}")
                 return self.stack, self.channels_last, 0
             return self.stack[lo:hi].to(dev), self.channels_last, lo
+        if hasattr(self.seq, "device_batch"):                            # FrameDir(decode="gpu"): decoded where they are used
+            return self.seq.device_batch(lo, hi, dev), True, lo
         batch = []
         for i in range(lo, hi):
             f = self.seq[i]
