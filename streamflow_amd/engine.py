@@ -34,9 +34,8 @@ class EngineOptions:
     `HotPathEngine(options=EngineOptions(split_solo=0))`, or from the shell for an experiment: SF_ENGINE_OPTS="split_solo=0,pw_fold=0"."""
     parallel_branches: bool = True   # independent chains of an iteration on a second stream
     split_solo: int = 2              # 0 / 2 / 4: sections without a concurrent branch run as half-batch chains on own streams
-    split_uneven: bool = False       # ... also when the clip count does not divide (a single clip, an odd batch: two unequal ranges of images).
-                                     # Off (round 6): one chain is faster there -- 1 clip 229.8 -> 237.2 ff/s, 3 clips 341.7 -> 348.9, one Spring
-                                     # clip 50.0 -> 50.8; even splits keep their chains (2 / 6 / 8 clips: +2-3 %; tools/clip_split_sweep.sh)
+                                     # when the clip count divides; one chain otherwise (round 6: 1 clip 229.8 -> 237.2 ff/s, 3 clips
+                                     # 341.7 -> 348.9, one Spring clip 50.0 -> 50.8 that way; even splits: +2-3 % with their chains)
     auto_split_k: bool = True        # let sf_gemm split K for small grids (changes summation order at toy shapes only)
     attn_chunk_rows: int = 0         # > 0 forces the chunked recompute of the attention matrix
     attn_k_splits: int = 3           # split-K of attn @ v (materialised matrix), <= 4
@@ -46,9 +45,6 @@ class EngineOptions:
     shadow_fused: bool = True        # ... written by their producers' epilogues instead of a pack pass
     hidden_f16: bool = True          # GEMM-to-GEMM tensors as fp16 in the f16x2 / f16 modes
     hidden_koct: bool = True         # ... as k-octet planes where the consumer takes them
-    split_handover: bool = False     # f16x3 (fp32_class): GEMM-to-GEMM tensors stored already split, hi + lo k-octet images (SF_LAYOUT_SPLIT_KOCT):
-                                     # bit-identical; the consumers run 7-10 % faster on two DMA-fed operands, the producers' k-octet epilogue
-                                     # costs more than that (fp32_class 182.6 -> 178.2 ff/s; tools/gemm_split_koct_bench.py): off
     pw_fold: bool = True             # pw residual folded into the weights (x3 handed over in fp16)
     koct_io: bool = True             # motion-encoder tensors between SK blocks as fp16 k-octets only (no fp32 planes)
     x2_f16: bool = True              # single-reader tensors as fp16 ROWS: x2 (ffn1.2 -> depthwise), qkv (-> temporal attention), v (-> GMA pack)
@@ -128,15 +124,12 @@ class SKBlockWeights:
         self.dw_single = False                # the K x K depthwise weights as one fp16 value (layer name '<block>.dw')
 
 
-def _scratch(buf: Planes, n_img: int, rows: int, f16: bool = False, koct: bool = False, split: bool = False) -> Planes:
+def _scratch(buf: Planes, n_img: int, rows: int, f16: bool = False, koct: bool = False) -> Planes:
     """Reinterpret a scratch allocation as contiguous [n_img][rows][P] planes (fp32, or fp16 values in the same memory;
-    koct: fp16 k-octet planes [ceil(rows/8)][P][8], the DMA-able image of the consuming GEMM; split: two such images per
-    image, hi then lo -- the f16x3 hand-over, as many bytes as the fp32 planes)."""
+    koct: fp16 k-octet planes [ceil(rows/8)][P][8], the DMA-able image of the consuming GEMM)."""
     rows_alloc = (rows + 7) // 8 * 8 if koct else rows
-    assert not split or (f16 and koct)
-    assert n_img * rows_alloc * (1 if (not f16 or split) else 0.5) <= buf.n_img * buf.rows, "scratch too small"
-    return Planes(buf.base, buf.off, rows_alloc * buf.P * (2 if split else 1), n_img, rows, buf.P, f16=f16, koct=f16 and koct,
-                  split=split)
+    assert n_img * rows_alloc * (0.5 if f16 else 1) <= buf.n_img * buf.rows, "scratch too small"
+    return Planes(buf.base, buf.off, rows_alloc * buf.P, n_img, rows, buf.P, f16=f16, koct=f16 and koct)
 
 
 def _handover(cx: ops.Ctx, buf: Planes, n_img: int, rows: int, P: int, consumer_rows: int, allow_koct: bool = True) -> Planes:
@@ -144,9 +137,6 @@ def _handover(cx: ops.Ctx, buf: Planes, n_img: int, rows: int, P: int, consumer_
     """Scratch view for a tensor that is written by one GEMM and read only as the B operand of the next: fp32 planes in
     the exact / f16x3 modes; in f16x2 fp16 values -- as k-octet planes when the consumer runs on the DMA-fed 128-row tile
     (both of its operands then go HBM/L2 -> LDS without touching registers), as fp16 rows otherwise."""
-    if cx.precision == ops.PRECISION_F16X3 and cx.split_handover and ops.uses_dma_tile(consumer_rows) and P % 4 == 0:
-        # f16x3: the (hi, lo) pair the consumer would compute, stored by the producer: same bytes, same values, both operands by DMA
-        return _scratch(buf, n_img, rows, f16=True, koct=True, split=True)
     f16 = hidden_f16_ok(cx, P)
     koct = f16 and allow_koct and ops.takes_koct(consumer_rows, rows) and cx.hidden_koct
     return _scratch(buf, n_img, rows, f16=f16, koct=koct)
@@ -431,19 +421,15 @@ class _Plan:
         self.graph_key = None
         self.graph_calls = 0
 
-
-def _level_maps(self, l: int) -> torch.Tensor:
-    """Level l of the row-major volumes as [pairs, clips * N, h_l, w_l] -- per pair the reference's corr_pyramid[l] (corr.py:13-21)
-    without its singleton dimension -- a strided VIEW of the (possibly row-pitched, _Plan.corr_pitch) storage; a copy for blocked volumes."""
-    hl, wl = self.h >> l, self.w >> l
-    if self.lvls is None:                      # blocked volumes (image = clip * pairs + pair): a row-major COPY, tests only
-        t = self.vol.levels()[l].view(self.Bc, self.Pn, self.P, hl, wl)
-        return t.permute(1, 0, 2, 3, 4).reshape(self.Pn, self.Bc * self.P, hl, wl)
-    pit = self.corr_pitch[l] if self.corr_pitch else wl
-    return self.lvls[l].view(self.Pn, self.Bc * self.P, hl, pit)[..., :wl]
-
-
-_Plan.level_maps = _level_maps
+    def level_maps(self, l: int) -> torch.Tensor:
+        """Level l of the row-major volumes as [pairs, clips * N, h_l, w_l] -- per pair the reference's corr_pyramid[l] (corr.py:13-21)
+        without its singleton dimension -- a strided VIEW of the (possibly row-pitched, _Plan.corr_pitch) storage; a copy for blocked volumes."""
+        hl, wl = self.h >> l, self.w >> l
+        if self.lvls is None:                      # blocked volumes (image = clip * pairs + pair): a row-major COPY, tests only
+            t = self.vol.levels()[l].view(self.Bc, self.Pn, self.P, hl, wl)
+            return t.permute(1, 0, 2, 3, 4).reshape(self.Pn, self.Bc * self.P, hl, wl)
+        pit = self.corr_pitch[l] if self.corr_pitch else wl
+        return self.lvls[l].view(self.Pn, self.Bc * self.P, hl, pit)[..., :wl]
 
 
 class HotPathEngine:
@@ -571,7 +557,7 @@ class HotPathEngine:
         return ops.Ctx(precision=self.precision,
                        split_ws=pl.splitws.tensor().view(-1) if self.auto_split_k else None,
                        shadows=o.shadows, shadow_fused=o.shadow_fused, flash_stats=o.flash_stats,
-                       hidden_f16=o.hidden_f16, hidden_koct=o.hidden_koct, split_handover=o.split_handover, pw_fold=o.pw_fold, x2_f16=o.x2_f16,
+                       hidden_f16=o.hidden_f16, hidden_koct=o.hidden_koct, pw_fold=o.pw_fold, x2_f16=o.x2_f16,
                        ffn_pairs=o.ffn_pairs, head_pairs=o.head_pairs, sk_tail=o.sk_tail, sk_tail_all=o.sk_tail_all)
 
     @staticmethod
@@ -636,7 +622,6 @@ class HotPathEngine:
     def _iteration(self, cx: ops.Ctx, pl: _Plan, with_mask: bool, fuse_mask: bool = False) -> None:
         W = self.W
         Bc, Pn, h, w, P, n = pl.Bc, pl.Pn, pl.h, pl.w, pl.P, pl.n
-        sk = lambda Wt, X, Y, fg=False: run_skblock(Wt, X, Y, pl.hid, pl.xa, pl.xb, h, w, fg, cx=cx)
         main = torch.cuda.current_stream()
         side = self._side if self.parallel_branches else main
         # the automatic split-K scratch is ONE buffer: only the main stream may use it while two streams run concurrently
@@ -668,50 +653,36 @@ class HotPathEngine:
             ops.refresh_shadow(pl.corr, cx)
         else:
             ops.corr_lookup(pl.lvls, pl.lvl_pair_stride, pl.coords1, pl.corr, Bc, Pn, h, w, cx=cx, pitch=pl.corr_pitch)
-        # image ranges of the chains: whole clips when the clip count divides, else (a single clip, an odd batch) two
-        # ranges of images -- every block but the flow head works image by image
+        # image ranges of the chains: whole clips when the clip count divides, else (a single clip, an odd batch) one chain
         nch = self.split_solo if (self.split_solo in (2, 4) and side is not main) else 1
-        if nch > 1 and Bc % nch == 0:
-            parts, by_clip = [(c * (n // nch), n // nch) for c in range(nch)], True
-        elif nch > 1 and n >= 2 and self.options.split_uneven:
-            parts, by_clip = [(0, (n + 1) // 2), ((n + 1) // 2, n // 2)], False
-        else:
-            parts, by_clip = [(0, n)], True
+        parts = [(c * (n // nch), n // nch) for c in range(nch)] if (nch > 1 and Bc % nch == 0) else [(0, n)]
         split = len(parts) > 1
 
-        # One scratch buffer: no automatic split-K while the chains run (context `cc`).  auto_splits() only fires for grids of
-        # fewer than 96 workgroups with K >= 256 (gemm_split.hip) -- never at the Sintel / KITTI / Spring shapes, whose
-        # smallest GEMM has 165 workgroups per clip -- so the two-chain schedule changes results (summation order) only at toy
-        # shapes; the bitwise test of the two schedules therefore runs with auto_split_k = False.
-        cc = cx.no_split()
-
-        def two_chains(fn):
-            """fn(image0, count): chain 0 on the main stream, the others on their own streams."""
+        def chains(fn):
+            """fn(image0, count, ctx) over every part: chain 0 on the main stream, the others on their own streams.
+            One scratch buffer: no automatic split-K while several chains run.  auto_splits() only fires for grids of fewer than
+            96 workgroups with K >= 256 (gemm_split.hip) -- never at the Sintel / KITTI / Spring shapes, whose smallest GEMM has
+            165 workgroups per clip -- so the chained schedule changes results (summation order) only at toy shapes; the bitwise
+            test of the two schedules therefore runs with auto_split_k = False."""
+            cc = cx.no_split() if split else cx
             for c in range(1, len(parts)):
                 sc = self._chain_streams[c - 1]
                 sc.wait_stream(main)
                 with torch.cuda.stream(sc):
-                    fn(*parts[c])
-            fn(*parts[0])
+                    fn(*parts[c], cc)
+            fn(*parts[0], cc)
             for c in range(1, len(parts)):
                 main.wait_stream(self._chain_streams[c - 1])
 
-        if split:
-            def corr_chain(i0, cnt):
-                hid, xa, xb = _part(pl.hid, i0, cnt), _part(pl.xa, i0, cnt), _part(pl.xb, i0, cnt)
-                run_skblock(W.convc1, _sub(pl.corr, i0, cnt), _sub(pl.cor256, i0, cnt), hid, xa, xb, h, w, True, cx=cc)
-                run_skblock(W.convc2, _sub(pl.cor256, i0, cnt), _sub(pl.cat256.slice(0, 192), i0, cnt), hid, xa, xb, h, w, cx=cc)
-            two_chains(corr_chain)
-        else:
-            sk(W.convc1, pl.corr, pl.cor256, True)                 # cor = gelu(convc1(corr))
-            sk(W.convc2, pl.cor256, pl.cat256.slice(0, 192))
+        def corr_chain(i0, cnt, cc):
+            hid, xa, xb = _part(pl.hid, i0, cnt), _part(pl.xa, i0, cnt), _part(pl.xb, i0, cnt)
+            run_skblock(W.convc1, _sub(pl.corr, i0, cnt), _sub(pl.cor256, i0, cnt), hid, xa, xb, h, w, True, cx=cc)   # cor = gelu(convc1(corr))
+            run_skblock(W.convc2, _sub(pl.cor256, i0, cnt), _sub(pl.cat256.slice(0, 192), i0, cnt), hid, xa, xb, h, w, cx=cc)
+        chains(corr_chain)
         join()
-        if split:                                                   # mf = cat(out, flow); flow rows kept by flow_update
-            two_chains(lambda i0, cnt: run_skblock(W.conv, _sub(pl.cat256, i0, cnt), _sub(pl.mf.slice(0, HDIM - 2), i0, cnt),
-                                                   _part(pl.hid, i0, cnt), _part(pl.xa, i0, cnt), _part(pl.xb, i0, cnt), h, w,
-                                                   cx=cc))
-        else:
-            sk(W.conv, pl.cat256, pl.mf.slice(0, HDIM - 2))
+        # mf = cat(out, flow); flow rows kept by flow_update
+        chains(lambda i0, cnt, cc: run_skblock(W.conv, _sub(pl.cat256, i0, cnt), _sub(pl.mf.slice(0, HDIM - 2), i0, cnt),
+                                               _part(pl.hid, i0, cnt), _part(pl.xa, i0, cnt), _part(pl.xb, i0, cnt), h, w, cx=cc))
         # a10: temporal transformer block over the T-1 tokens of each pixel (update.py:481-484,770), side stream
         fork()
         with on_side():
@@ -720,7 +691,7 @@ class HotPathEngine:
                 ops.temporal_block(W.temporal, pl.mf, pl.mft, Pn, (W.ln1_w, W.ln1_b), (W.ln2_w, W.ln2_b), cx=cs)
             else:
                 # LayerNorm / attention outputs have ONE reader, a GEMM: in the f16x2 mode they leave as its k-octet operand
-                ko = lambda buf, M: (lambda t: t if (t.koct and not t.split) else buf)(_handover(cs, buf, pl.n, HDIM, P, consumer_rows=M))
+                ko = lambda buf, M: (lambda t: t if t.koct else buf)(_handover(cs, buf, pl.n, HDIM, P, consumer_rows=M))
                 ln, att = ko(pl.ln128, W.qkv.M), ko(pl.att128, W.proj.M)
                 ops.layernorm_cm(pl.mf, W.ln1_w, W.ln1_b, ln)
                 # qkv has ONE reader, the attention core: fp16 rows where the fp16 hand-over is active (EPE-neutral)
@@ -799,25 +770,18 @@ class HotPathEngine:
         if not gma_in_chains:
             join()
         # "gru": SKBlock(640 -> 128) over cat[nets, inps, mf, mfg, mft]; new nets overwrite the nets slice
-        if split:
-            def gru_chain(i0, cnt):
-                hid, xa, xb = _part(pl.hid, i0, cnt), _part(pl.xa, i0, cnt), _part(pl.xb, i0, cnt)
-                if gma_in_chains:
-                    ops.gma_flash_aggregate(self._flash_ws_sub(pl, i0, cnt), None, _sub(pl.mf, i0, cnt), W.gamma, _sub(pl.mfg, i0, cnt),
-                                            self.flash_qk_products, use_stats=True, cx=cc)
-                    if side is not main:                            # the temporal block's output (side stream) is a GRU input
-                        torch.cuda.current_stream().wait_stream(side)
-                run_skblock(W.gru, _sub(pl.concat, i0, cnt), _sub(pl.nets, i0, cnt), hid, xa, xb, h, w, cx=cc)
-                if by_clip:     # flow head sees all T-1 hidden states of a clip jointly (update.py:774): clips i0 / Pn ..
-                    run_skblock(W.flow_head, _sub(pl.nets_grouped, i0 // Pn, cnt // Pn),
-                                _sub(pl.delta_fh, i0 // Pn, cnt // Pn), hid, xa, xb, h, w, cx=cc)
-            two_chains(gru_chain)
-            if not by_clip:
-                sk(W.flow_head, pl.nets_grouped, pl.delta_fh)
-        else:
-            sk(W.gru, pl.concat, pl.nets)
-            # flow head sees all T-1 hidden states of a clip jointly (update.py:774)
-            sk(W.flow_head, pl.nets_grouped, pl.delta_fh)
+        def gru_chain(i0, cnt, cc):
+            hid, xa, xb = _part(pl.hid, i0, cnt), _part(pl.xa, i0, cnt), _part(pl.xb, i0, cnt)
+            if gma_in_chains:
+                ops.gma_flash_aggregate(self._flash_ws_sub(pl, i0, cnt), None, _sub(pl.mf, i0, cnt), W.gamma, _sub(pl.mfg, i0, cnt),
+                                        self.flash_qk_products, use_stats=True, cx=cc)
+                if side is not main:                                # the temporal block's output (side stream) is a GRU input
+                    torch.cuda.current_stream().wait_stream(side)
+            run_skblock(W.gru, _sub(pl.concat, i0, cnt), _sub(pl.nets, i0, cnt), hid, xa, xb, h, w, cx=cc)
+            # flow head sees all T-1 hidden states of a clip jointly (update.py:774): clips i0 / Pn ..
+            run_skblock(W.flow_head, _sub(pl.nets_grouped, i0 // Pn, cnt // Pn), _sub(pl.delta_fh, i0 // Pn, cnt // Pn),
+                        hid, xa, xb, h, w, cx=cc)
+        chains(gru_chain)
         if with_mask:                                               # update.py:756-759,777
             ops.gemm(W.mask0, pl.nets, pl.m256, EPI_RELU, hw=(h, w), cx=cx)
             if not fuse_mask:                                       # (fused: mask.2 runs inside sf_mask_upsample, after the loop)
