@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 129
+#define SF_VERSION 130
 
 enum {
     SF_OK = 0,
@@ -827,6 +827,50 @@ int sf_clips_to_flows(const SfPairPtrs* pairs, int64_t clip_stride, int64_t ch_s
 #define SF_PNG_MAX_ROW_BYTES 40960 /* 5120 pixels of 16-bit RGBA; the kernel keeps one row of this size and 4 KiB more in LDS */
 int sf_png_unfilter(const uint8_t* scan, int64_t scan_image_stride, int n_images, int h, int w, int bpp, uint8_t* out,
                     int64_t out_image_stride, int64_t out_row_stride, int swap16, void* stream);
+
+/* ---- PNG output: adaptive row filter and Huffman-only deflate of a batch of device images (RFC 1950 / 1951; PNG specification 9, 12.8) --
+ * sf_png_encode: image i is h rows of w bpp bytes at img + i img_image_stride + y img_row_stride (bpp as for sf_png_unfilter; with
+ *   swap16 != 0 the 16-bit samples are in host order and are filtered and written big-endian; needs an even bpp).  out + i
+ *   out_image_stride receives a complete zlib stream and out_bytes[i] (device memory) its length:
+ *     `78 01`; one dynamic-Huffman block per band of SF_PNG_ENC_BAND_ROWS scanlines, literals and end-of-block only, BFINAL on the
+ *     last; the big-endian Adler-32 of the scanlines.
+ *   A scanline is the filter-type byte and the w bpp filtered bytes; the type of a row is the one whose filtered bytes have the
+ *   smallest sum of min(v, 256 - v) (libpng's heuristic), ties to the lowest type; row 0 has a zero row above it.
+ *   A block: BFINAL, BTYPE = 2, HLIT = 0, HDIST = 1, HCLEN = 15; 19 code-length code lengths; 257 literal / end-of-block lengths and two
+ *   distance lengths of 1 (as zlib writes a block without matches), each as its own code-length symbol 0 .. 15 (no repeat codes: a
+ *   header is at most 1887 bits against some 100 KB of scanlines); the literals; the end-of-block.  Code lengths are at most 15
+ *   (literals) and 7 (code-length alphabet) bits, codes canonical.  Lengths: the used symbols ranked by (frequency, symbol); Huffman's
+ *   algorithm on two queues, a leaf taken when its weight is <= the front node's; leaves per depth, depths above the limit counted at
+ *   the limit; while the Kraft sum exceeds 1, one code leaves the limit and one code of the deepest shorter length becomes two codes
+ *   one bit longer; lengths handed out along the rank, longest first.  If the literal table costs more bits than the fixed table
+ *   (8 bits for 0 .. 254, 9 for 255 and end-of-block) that table is used.  A band always has two used symbols (a byte and the
+ *   end-of-block), so a band of one value gets two 1-bit codes.  tests/png_encode_cases.py restates all of it; the output equals that
+ *   restatement byte for byte, and two runs are bitwise equal.
+ *   SF_PNG_ENC_BAND_ROWS = 32: the stream size is flat over 8 .. 64 rows (-0.4 % .. +0.4 % of zlib's Z_HUFFMAN_ONLY on smooth
+ *   436 x 1024 images); 32 rows make 14 blocks of a 436-row frame, enough workgroups per image, with a header below
+ *   0.3 % of a block.
+ * sf_png_encode_bound(h, w, bpp): no stream is longer, whatever the image holds: 2 + ceil((nb 1896 + 9 h (1 + w bpp)) / 8) + 4 rounded
+ *   up to a multiple of 4, nb = ceil(h / SF_PNG_ENC_BAND_ROWS): a header is at most 17 + 57 + 259 x 7 = 1887 bits, and the literals
+ *   of a band of N bytes at most 9 N + 9 bits because the fixed table above replaces a costlier one.  -1 for a shape sf_png_encode
+ *   refuses with SF_ERR_BAD_ARG.  The bytes of a slot between the stream's end and the bound are unspecified (the call clears them
+ *   itself: `out` need not be zeroed); nothing beyond the bound is written.
+ * sf_png_encode_ws_bytes: the workspace (filtered scanlines, per-band tables); -1 for a refused shape or n_images.
+ * One memset and four launches (filter: a wave per row; tables: a workgroup per band; offsets: a thread per image; pack: a workgroup
+ *   per band, bits ORed in with vector atomics); dependencies between workgroups are launch boundaries and every trip count depends
+ *   on (n_images, h, w, bpp) alone.  No host synchronisation.
+ *   SF_ERR_BAD_ARG before any launch for: null pointers, n_images outside 1 .. 65535, h or w < 1, a bpp outside the set, swap16 with an
+ *   odd bpp, h (1 + w bpp) >= 2^31, img_row_stride < w bpp, img_image_stride < (h - 1) img_row_stride + w bpp, out_image_stride below
+ *   the bound, out or out_image_stride not a multiple of 4, out_bytes not 8-byte aligned, ws_bytes too small.  SF_ERR_UNSUPPORTED for
+ *   w bpp > SF_PNG_MAX_ROW_BYTES.
+ * sf_flow_to_kitti16: flow [n][2][h][w] fp32 -> out [n][h][w][3] uint16 in host order = (64 u + 32768, 64 v + 32768, 1), flow_io.kitti_encode
+ *   for float32 input: the product (exact) and the sum are rounded to fp32 one after the other, the result is truncated.  Values
+ *   below 0 and NaN give 0, values of 65535 or more give 65535.  Limits: n <= 65535, h * w < 2^30. */
+#define SF_PNG_ENC_BAND_ROWS 32
+int64_t sf_png_encode_bound(int h, int w, int bpp);
+int64_t sf_png_encode_ws_bytes(int n_images, int h, int w, int bpp);
+int sf_png_encode(const uint8_t* img, int64_t img_image_stride, int64_t img_row_stride, int n_images, int h, int w, int bpp,
+                  int swap16, uint8_t* out, int64_t out_image_stride, int64_t* out_bytes, void* ws, int64_t ws_bytes, void* stream);
+int sf_flow_to_kitti16(const float* flow, uint16_t* out, int n, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -185,6 +185,10 @@ SIGNATURES = {
     "sf_frames_to_clips": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_clips_to_flows": (_i, [C.POINTER(SfPairPtrs), _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sf_png_unfilter": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp]),
+    "sf_png_encode_bound": (_i64, [_i, _i, _i]),
+    "sf_png_encode_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "sf_png_encode": (_i, [_vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sf_flow_to_kitti16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -210,7 +214,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 129:
+    if lib.sf_version() < 130:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -65,50 +65,81 @@ def predict_clips_warm_start(model: Callable, clips: Sequence[Sequence[torch.Ten
     return out
 
 
-def colour_images(flows: Sequence[torch.Tensor], rad_max=None) -> List:
-    """numpy uint8 [H, W, 3] colour-wheel images of device flows [2, H, W] (or [1, 2, H, W]), in order.  Fields of equal shape
-    are stacked and coloured by ONE ops.flow_to_image call (each still on its own scale unless `rad_max` fixes one)."""
+def _colour_batches(flows: Sequence[torch.Tensor], rad_max=None) -> List[Tuple[List[int], torch.Tensor]]:
+    """[(indices into `flows`, device uint8 [k, H, W, 3])]: fields of equal shape are stacked and coloured by ONE ops.flow_to_image
+    call (each still on its own scale unless `rad_max` fixes one)."""
     from . import ops
     fields = [f[0] if f.dim() == 4 else f for f in flows]
-    images: List = [None] * len(fields)
     by_shape = {}
     for i, f in enumerate(fields):
         by_shape.setdefault((tuple(f.shape), f.device), []).append(i)
+    out = []
     for idx in by_shape.values():
         batch = torch.stack([fields[i].detach().float() for i in idx]).contiguous()
         if not batch.is_cuda and torch.cuda.is_available():
             batch = batch.to(torch.device("cuda", torch.cuda.current_device()))
-        out = ops.flow_to_image(batch, rad_max=rad_max).cpu().numpy()
+        out.append((idx, ops.flow_to_image(batch, rad_max=rad_max)))
+    return out
+
+
+def colour_images(flows: Sequence[torch.Tensor], rad_max=None) -> List:
+    """numpy uint8 [H, W, 3] colour-wheel images of device flows [2, H, W] (or [1, 2, H, W]), in order."""
+    images: List = [None] * len(flows)
+    for idx, batch in _colour_batches(flows, rad_max):
+        host = batch.cpu().numpy()
         for k, i in enumerate(idx):
-            images[i] = out[k]
+            images[i] = host[k]
     return images
 
 
-def vis_flow(flows_result: Sequence[torch.Tensor], save_dir: str = "flow_result", rad_max=None) -> List[str]:
+def _check_png_encode(png_encode: str) -> bool:
+    if png_encode not in ("host", "gpu"):
+        raise ValueError(f"png_encode must be 'host' or 'gpu', got {png_encode!r}")
+    return png_encode == "gpu"
+
+
+def write_colour_pngs(flows: Sequence[torch.Tensor], paths: Sequence[str], rad_max=None, png_encode: str = "host") -> None:
+    """The colour-wheel image of flows[i] as the PNG file paths[i].  png_encode="host": flow_io.write_png (filter 0, zlib level 6) on
+    images copied to the host; "gpu": png_gpu.encode_batch on the device images, so only compressed streams cross to the host.  The
+    pixels are the same, the file bytes differ."""
+    from . import flow_io, png_gpu
+    gpu = _check_png_encode(png_encode)
+    for idx, batch in _colour_batches(flows, rad_max):
+        if gpu:
+            png_gpu.encode_batch(batch, [paths[i] for i in idx])
+        else:
+            host = batch.cpu().numpy()
+            for k, i in enumerate(idx):
+                flow_io.write_png(paths[i], host[k])
+
+
+def vis_flow(flows_result: Sequence[torch.Tensor], save_dir: str = "flow_result", rad_max=None, png_encode: str = "host") -> List[str]:
     """The reference's `vis_flow` (demo.py:536-548) with a PNG sequence ``save_dir/frame_%04d.png`` in place of its mp4 (no video
     encoder here).  flows_result: flow fields [2, H, W] as `predict_frames` returns them (CPU tensors are moved to the current
     GPU: the colouring is the sf_flow_to_image kernel, all fields of equal shape in one call).  `rad_max` fixes one scale for the
-    whole sequence (no flicker between frames); default: each frame on its own scale, as the reference.  Returns the paths."""
+    whole sequence (no flicker between frames); default: each frame on its own scale, as the reference.  png_encode="gpu": the files
+    are encoded on the GPU too (write_colour_pngs).  Returns the paths."""
     import os
-    from . import flow_io
     os.makedirs(save_dir, exist_ok=True)
-    paths = []
-    for i, img in enumerate(colour_images(flows_result, rad_max=rad_max)):
-        paths.append(os.path.join(save_dir, "frame_%04d.png" % i))
-        flow_io.write_png(paths[-1], img)
+    paths = [os.path.join(save_dir, "frame_%04d.png" % i) for i in range(len(flows_result))]
+    write_colour_pngs(flows_result, paths, rad_max=rad_max, png_encode=png_encode)
     return paths
 
 
 def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, clips_per_step: int = 8, mode: str = "sintel",
-                                  save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host") -> int:
+                                  save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host",
+                                  png_encode: str = "host") -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames: video.FrameDir ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
     are coloured on the GPU and written as ``save_dir/frame_%04d.png`` (numbered by pair) and, with `flo_dir`, as Middlebury
     ``flo_dir/frame_%04d.flo``.  png_decode="gpu": the frames' PNG rows are unfiltered on the GPU (video.FrameDir(decode="gpu")), the
-    same bytes as the host decoder's.  Runs on the current GPU.  Returns the number of pairs."""
+    same bytes as the host decoder's.  png_encode="gpu": the colour images are filtered and deflated on the GPU
+    (png_gpu.encode_batch: no uncompressed image crosses to the host; the same pixels, other file bytes).  Runs on the current GPU.
+    Returns the number of pairs."""
     import os
     from . import flow_io, video
     from .model import StreamFlowT4
+    _check_png_encode(png_encode)
     frames = video.FrameDir(path, decode=png_decode)
     if not torch.cuda.is_available():
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
@@ -120,13 +151,13 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     written = [0]
 
     def sink(first_pair: int, flows: torch.Tensor) -> None:
-        images = colour_images(list(flows), rad_max=rad_max) if save_dir else []
-        host = flows.cpu().numpy() if flo_dir else None
-        for k in range(flows.shape[0]):
-            name = "frame_%04d" % (first_pair + k)
-            if save_dir:
-                flow_io.write_png(os.path.join(save_dir, name + ".png"), images[k])
-            if flo_dir:
+        names = ["frame_%04d" % (first_pair + k) for k in range(flows.shape[0])]
+        if save_dir:
+            write_colour_pngs(list(flows), [os.path.join(save_dir, name + ".png") for name in names], rad_max=rad_max,
+                              png_encode=png_encode)
+        if flo_dir:
+            host = flows.cpu().numpy()
+            for k, name in enumerate(names):
                 flow_io.write_flo(os.path.join(flo_dir, name + ".flo"), host[k].transpose(1, 2, 0))
         written[0] += int(flows.shape[0])
 
@@ -148,10 +179,13 @@ def main(argv=None) -> int:
     ap.add_argument("--mode", default="sintel", choices=("sintel", "kitti"))
     ap.add_argument("--png-decode", default="gpu", choices=("gpu", "host"),
                     help="where the frames' PNG rows are unfiltered (the same bytes either way)")
+    ap.add_argument("--png-encode", default="gpu", choices=("gpu", "host"),
+                    help="where the colour images are filtered and deflated (the same pixels either way, other file bytes)")
     ap.add_argument("--rad-max", type=float, default=None, help="one colour scale for the whole video (default: per frame)")
     a = ap.parse_args(argv)
     n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
-                                      save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode)
+                                      save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode,
+                                      png_encode=a.png_encode)
     print(f"{n} flow fields -> {a.out}" + (f", {a.flo}" if a.flo else ""))
     return 0
 

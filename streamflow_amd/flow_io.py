@@ -117,6 +117,20 @@ def write_png(path: str, img: np.ndarray) -> None:
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+def png_file(idat_stream: bytes, h: int, w: int, depth: int, channels: int) -> bytes:
+    """The bytes of a non-interlaced PNG file around a finished zlib stream of its scanlines (the host half of the GPU encoder,
+    ops.png_encode / png_gpu.encode_batch): signature, IHDR, one IDAT, IEND, the CRCs from zlib.crc32."""
+    if depth not in (8, 16) or channels not in (1, 2, 3, 4) or h < 1 or w < 1:
+        raise ValueError(f"png_file: h = {h}, w = {w}, bit depth {depth}, {channels} channels")
+    ctype = {1: 0, 2: 4, 3: 2, 4: 6}[channels]
+
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(tag)) & 0xFFFFFFFF)
+
+    return (_PNG_SIG + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0)) + chunk(b"IDAT", bytes(idat_stream)) +
+            chunk(b"IEND", b""))
+
+
 def png_scanlines(path: str) -> Tuple[np.ndarray, int, int, int, int]:
     """The inflated IDAT stream of a non-interlaced 8/16-bit gray / gray+alpha / RGB / RGBA PNG, still filtered:
     (raw uint8 [h * (1 + w * bpp)], h, w, bit depth, channels), bpp = channels * depth / 8.  Row y is raw[y * (1 + w * bpp):][:1 + w * bpp],

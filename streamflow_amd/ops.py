@@ -1460,6 +1460,48 @@ def png_unfilter(scan: torch.Tensor, h: int, w: int, bpp: int, out: Optional[tor
     return out
 
 
+@on_tensor_device
+def png_encode(images: torch.Tensor):
+    """The zlib streams of a PNG's IDAT chunk for a batch of device images (sf_png_encode: adaptive row filter and Huffman-only
+    deflate, csrc/png_encode.hip; the host half is flow_io.png_file): images [n, H, W, C] uint8 or torch.uint16 (host order; written
+    big-endian) on the GPU, C = 1 .. 4, the samples of a row contiguous, any row and image strides.  Returns (streams uint8
+    [n, sf_png_encode_bound], lengths int64 [n]) on the same GPU: stream i is streams[i, :lengths[i]], the bytes behind it are
+    unspecified.  Enqueued on the current stream, no synchronisation."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda:
+        raise RuntimeError(f"png_encode: images must be on the GPU (got {getattr(images, 'device', type(images).__name__)}); "
+                           "there is no CPU fallback -- flow_io.write_png is the host-side path")
+    if images.dtype not in (torch.uint8, torch.uint16) or images.dim() != 4 or images.numel() == 0 or images.shape[3] > 4:
+        raise RuntimeError(f"png_encode: expected uint8 / uint16 [n, H, W, C <= 4], got {images.dtype} {tuple(images.shape)}")
+    n, h, w, c = (int(v) for v in images.shape)
+    size = images.element_size()
+    if images.stride(3) != 1 or images.stride(2) != c or images.stride(1) < w * c or (n > 1 and images.stride(0) < (h - 1) * images.stride(1) + w * c):
+        raise RuntimeError(f"png_encode: the samples of a row must be contiguous and rows / images must not overlap (strides {images.stride()})")
+    lib = _lib.load()
+    bound, ws_bytes = lib.sf_png_encode_bound(h, w, c * size), lib.sf_png_encode_ws_bytes(n, h, w, c * size)
+    if bound < 0 or ws_bytes < 0:
+        raise RuntimeError(f"png_encode: n = {n}, h = {h}, w = {w}, bpp = {c * size} is outside what sf_png_encode takes")
+    streams = torch.empty(n, bound, dtype=torch.uint8, device=images.device)
+    lengths = torch.empty(n, dtype=torch.int64, device=images.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=images.device)
+    image_stride = images.stride(0) if n > 1 else (h - 1) * images.stride(1) + w * c
+    _lib.check(lib.sf_png_encode(images.data_ptr(), image_stride * size, images.stride(1) * size, n, h, w, c * size, 1 if size == 2 else 0,
+                                 streams.data_ptr(), bound, lengths.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream()), "sf_png_encode")
+    return streams, lengths
+
+
+@on_tensor_device
+def flow_to_kitti16(flows: torch.Tensor) -> torch.Tensor:
+    """KITTI flow codes of device flows (sf_flow_to_kitti16; flow_io.kitti_encode for float32): flows fp32 [N, 2, H, W] -> torch.uint16
+    [N, H, W, 3] = (64 u + 2^15, 64 v + 2^15, 1), truncated; NaN and values below 0 give 0, values above 65535 give 65535."""
+    _dev_check(flows)
+    if flows.dim() != 4 or flows.shape[1] != 2 or flows.numel() == 0:
+        raise RuntimeError(f"flow_to_kitti16: expected flows [N, 2, H, W], got {tuple(flows.shape)}")
+    n, _, h, w = flows.shape
+    out = torch.empty(n, h, w, 3, dtype=torch.uint16, device=flows.device)
+    _lib.check(_lib.load().sf_flow_to_kitti16(flows.data_ptr(), out.data_ptr(), n, h, w, _lib.stream()), "sf_flow_to_kitti16")
+    return out
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None

@@ -1,9 +1,13 @@
-"""PNG files -> decoded frames on the GPU: the inflate on the host (zlib, in a thread pool: it releases the GIL), the row unfilter
+"""PNG files <-> frames on the GPU.  Decoding: the inflate on the host (zlib, in a thread pool: it releases the GIL), the row unfilter
 as one sf_png_unfilter launch for the whole batch (csrc/png_unfilter.hip).  flow_io.read_png's Average / Paeth branches walk a row
 byte by byte in Python, and libpng-written files (Sintel, KITTI, exported videos) are mostly Paeth rows; here that arithmetic runs
 where the decoded bytes are wanted anyway (sf_frames_to_clips, sf_flow_score_batch).
 
-There is no fallback: without a GPU `decode_batch` raises, and flow_io.read_png stays the host-side decoder.
+Encoding (`encode_batch`): the adaptive row filter and a Huffman-only deflate as one sf_png_encode call for the whole batch
+(csrc/png_encode.hip); only the compressed streams cross to the host, where the chunk framing, the CRC-32 and the file writes run in
+the same thread pool.
+
+There is no fallback: without a GPU `decode_batch` and `encode_batch` raise; flow_io.read_png / write_png stay the host-side codec.
 """
 from __future__ import annotations
 
@@ -111,3 +115,38 @@ def decode_frames(paths: Sequence[str], device, threads: Optional[int] = None) -
         for idx in groups.values():
             out[torch.tensor(idx, device=dev)] = to_rgb8(_unfilter([got[i] for i in idx], dev))
         return out
+
+
+def encode_batch(images: torch.Tensor, paths: Sequence[str], threads: Optional[int] = None) -> List[int]:
+    """Device images [n, H, W, C] uint8 or torch.uint16 (C = 1 .. 4) -> the PNG files `paths`, image i decoding to images[i] exactly
+    (flow_io.read_png, any PNG reader).  One ops.png_encode call on the current stream; the n stream lengths are copied first, then
+    only the used bytes of every slot (pinned memory); flow_io.png_file and the file writes run in the thread pool.  Returns the
+    files' sizes in bytes."""
+    from . import ops
+    paths = list(paths)
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or len(paths) != images.shape[0] or not paths:
+        raise ValueError(f"png_gpu.encode_batch: images [n, H, W, C] and n paths (got {getattr(images, 'shape', type(images).__name__)}, "
+                         f"{len(paths)} paths)")
+    _need_gpu(images.device)
+    n, h, w, c = (int(v) for v in images.shape)
+    depth = 8 * images.element_size()
+    streams, lengths = ops.png_encode(images)
+    used = [int(v) for v in lengths.cpu()]
+    start = [sum(used[:i]) for i in range(n)]
+    host = torch.empty(sum(used), dtype=torch.uint8, pin_memory=True)
+    for i in range(n):
+        host[start[i]:start[i] + used[i]].copy_(streams[i, :used[i]], non_blocking=True)
+    torch.cuda.current_stream(images.device).synchronize()
+    data = host.numpy()
+
+    def write(i: int) -> int:
+        blob = flow_io.png_file(data[start[i]:start[i] + used[i]].tobytes(), h, w, depth, c)
+        with open(paths[i], "wb") as f:
+            f.write(blob)
+        return len(blob)
+
+    k = min(pool_threads(threads), n)
+    if k == 1:
+        return [write(i) for i in range(n)]
+    with ThreadPoolExecutor(max_workers=k) as ex:
+        return list(ex.map(write, range(n)))

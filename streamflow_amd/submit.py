@@ -46,34 +46,44 @@ def _colour(flows: List[torch.Tensor], keep: List[int]) -> dict:
     return {i: imgs[k] for k, i in enumerate(keep)}
 
 
-def _write_sintel_clip(flows: List[torch.Tensor], ids: List[int], output_path: str, dstype: str, scene: str, vis: bool) -> None:
-    """flows: nframes - 1 unpadded fields [2, H, W]; ids: the clip's frame ids (-1: pair already written by an earlier clip)."""
+def _write_sintel_clip(flows: List[torch.Tensor], ids: List[int], output_path: str, dstype: str, scene: str, vis: bool,
+                       png_encode: str = "host") -> None:
+    """flows: nframes - 1 unpadded fields [2, H, W]; ids: the clip's frame ids (-1: pair already written by an earlier clip).
+    png_encode="gpu": the colour images are encoded on the device (png_gpu.encode_batch: the same pixels, other file bytes)."""
     assert len(flows) == len(ids) - 1
+    if png_encode not in ("host", "gpu"):
+        raise ValueError(f"png_encode must be 'host' or 'gpu', got {png_encode!r}")
     output_dir = os.path.join(output_path, dstype, scene)
     os.makedirs(output_dir, exist_ok=True)
     keep = [i for i in range(len(flows)) if ids[i] != -1]
-    images = _colour(flows, keep) if vis else {}
+    pngs = {i: os.path.join(output_path, dstype, "%s-%d.png" % (scene, ids[i] + 1)) for i in keep}
+    if vis and keep and png_encode == "gpu":
+        from . import ops, png_gpu
+        png_gpu.encode_batch(ops.flow_to_image(torch.stack([flows[i].float() for i in keep]).contiguous()), [pngs[i] for i in keep])
+    images = _colour(flows, keep) if vis and png_encode == "host" else {}
     for i in keep:
         flow_io.write_flo(os.path.join(output_dir, "frame%04d.flo" % (ids[i] + 1)), flows[i].permute(1, 2, 0).float().cpu().numpy())
-        if vis:
-            flow_io.write_png(os.path.join(output_path, dstype, "%s-%d.png" % (scene, ids[i] + 1)), images[i])
+        if i in images:
+            flow_io.write_png(pngs[i], images[i])
 
 
 @torch.no_grad()
 def create_sintel_submission_mf(args, model: Callable, iters: int, output_path: str = "sintel_submission", nframes: int = 3,
-                                vis: bool = True, device: Optional[torch.device] = None) -> None:
-    """Create the submission tree for the Sintel leaderboard (every clip from a cold start)."""
+                                vis: bool = True, device: Optional[torch.device] = None, png_encode: str = "host") -> None:
+    """Create the submission tree for the Sintel leaderboard (every clip from a cold start).  png_encode: see _write_sintel_clip."""
     _eval_mode(model)
     dev = device or model_device(model, torch.device("cpu"))
     for dstype in ("clean", "final"):
         for scene, imgs, _, _ in sintel_scenes(args.sintel_root, "test", dstype):
             for first, ids in sintel_clip_schedule(len(imgs), nframes):
-                _write_sintel_clip(run_clip(model, imgs[first:first + nframes], dev, iters), ids, output_path, dstype, scene, vis)
+                _write_sintel_clip(run_clip(model, imgs[first:first + nframes], dev, iters), ids, output_path, dstype, scene, vis,
+                                   png_encode)
 
 
 @torch.no_grad()
 def create_sintel_submission_mf_warmup(args, model: Callable, iters: int, output_path: str = "sintel_submission",
-                                       nframes: int = 3, vis: bool = True, device: Optional[torch.device] = None) -> None:
+                                       nframes: int = 3, vis: bool = True, device: Optional[torch.device] = None,
+                                       png_encode: str = "host") -> None:
     """Create the submission tree for the Sintel leaderboard with the warm-start chain: inside a scene every clip starts from the
     previous clip's low-resolution flows pushed forward along themselves; the chain restarts with every scene (the reference's
     `flow_prev = None`, which `demo.predict_clips_warm_start` spells as zero flows so that the model also returns the
@@ -91,7 +101,7 @@ def create_sintel_submission_mf_warmup(args, model: Callable, iters: int, output
                     yield padder.pad_list(read_clip(imgs[first:first + nframes], dev))
 
             for (_, ids), flows in zip(schedule, predict_clips_warm_start(model, clips(), iters=iters)):
-                _write_sintel_clip([padder.unpad(f[0]) for f in flows], ids, output_path, dstype, scene, vis)
+                _write_sintel_clip([padder.unpad(f[0]) for f in flows], ids, output_path, dstype, scene, vis, png_encode)
 
 
 @torch.no_grad()
@@ -119,9 +129,13 @@ def create_spring_submission_mf(args, model: Callable, iters: int, output_path: 
 
 @torch.no_grad()
 def create_kitti_submission_mf(args, model: Callable, iters: int, output_path: str = "kitti_submission", nframes: int = 3,
-                               vis_path: Optional[str] = None, device: Optional[torch.device] = None) -> None:
+                               vis_path: Optional[str] = None, device: Optional[torch.device] = None, png_encode: str = "host") -> None:
     """Create the submission folder for the KITTI-2015 leaderboard from the multi-frame test split: one 16-bit PNG per sequence
-    (the flow of frames 10 -> 11).  Sequences are those present under ``testing/image_2`` (the reference walks 000000 .. 000199)."""
+    (the flow of frames 10 -> 11).  Sequences are those present under ``testing/image_2`` (the reference walks 000000 .. 000199).
+    png_encode="gpu": the codes come from ops.flow_to_kitti16 and both files from png_gpu.encode_batch (the same pixels as the host
+    writers', other file bytes)."""
+    if png_encode not in ("host", "gpu"):
+        raise ValueError(f"png_encode must be 'host' or 'gpu', got {png_encode!r}")
     _eval_mode(model)
     dev = device or model_device(model, torch.device("cpu"))
     image_root, _, seqs = kitti_mf_sequences(args.multi_root, "testing")
@@ -131,6 +145,13 @@ def create_kitti_submission_mf(args, model: Callable, iters: int, output_path: s
     for seq in seqs:
         flow = run_clip(model, kitti_mf_clip(image_root, seq, nframes), dev, iters)[-1]       # default mode, not 'kitti': submit_mf.py:711
         frame_name = seq + "_10.png"
+        if png_encode == "gpu":
+            from . import ops, png_gpu
+            field = flow.float()[None].contiguous()
+            png_gpu.encode_batch(ops.flow_to_kitti16(field), [os.path.join(output_path, frame_name)])
+            if vis_path is not None:
+                png_gpu.encode_batch(ops.flow_to_image(field), [os.path.join(vis_path, "flow", frame_name)])
+            continue
         image = _colour([flow], [0])[0] if vis_path is not None else None
         flow_io.write_flow_kitti(os.path.join(output_path, frame_name), flow.permute(1, 2, 0).float().cpu().numpy())
         if image is not None:
