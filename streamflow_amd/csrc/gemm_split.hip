@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
     if (kDmaA) issue_a(kt_beg, 0);
     else opa.load(kt_beg * BK, ca.off, ra);
     if (kDmaB) issue_b(kt_beg, 0);
-    if (conv) opb.load(kt_beg * BK, conv_off(kt_beg * BK), rb, conv_shift(kt_beg * BK));
+    if (conv) opb.load(kt_beg * BK, conv_off(kt_beg * BK), rb, conv_shift(kt_beg * BK), conv_tap(kt_beg * BK));
     else opb.load(kt_beg * BK, cb.off, rb);
     if (!kDmaA) opa.template store<SA>(kt_beg * BK, sA[0], sA[SA ? 1 : 0], ra);
     opb.template store<SB>(kt_beg * BK, sB[0], sB[SB ? 1 : 0], rb, conv ? conv_tap(kt_beg * BK) : -1);
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
             else opa.load((kt + 1) * BK, ca.off, ra);
             if (kDmaB) issue_b(kt + 1, abuf ^ 1);
 #ifndef SF_ABLATE_B          // timing ablation only (wrong results): B tile staged once, never refreshed
-            if (conv) opb.load((kt + 1) * BK, conv_off((kt + 1) * BK), rb, conv_shift((kt + 1) * BK));
+            if (conv) opb.load((kt + 1) * BK, conv_off((kt + 1) * BK), rb, conv_shift((kt + 1) * BK), conv_tap((kt + 1) * BK));
             else opb.load((kt + 1) * BK, cb.off, rb);
 #endif
         }
@@ -745,7 +745,8 @@ int gemm_split_dispatch_inner(const SfGemm& g, hipStream_t st) {
     } else {
         a.a_bytes = span_bytes(g.a_layout, g.M, g.K, g.lda, 0, 0);
     }
-    a.b_bytes = span_bytes(g.b_layout, g.N, g.K, g.ldb, g.b_group, g.b_group_stride);
+    // (implicit 3x3 conv: K counts the nine taps, the image has K / 9 rows)
+    a.b_bytes = span_bytes(g.b_layout, g.N, g.conv3x3 ? g.K / 9 : g.K, g.ldb, g.b_group, g.b_group_stride);
     if (a.a_bytes >= ((int64_t)1 << 31) || a.b_bytes >= ((int64_t)1 << 31))
         return fail(SF_ERR_UNSUPPORTED, "sf_gemm(f16x3): operand image larger than 2 GiB (32-bit buffer offsets)");
     // tile choice: the 128-row tile moves the fewest bytes per MAC; drop to 64/32 rows when padding M would

@@ -102,12 +102,15 @@ struct Operand {
 
     // implicit 3x3 convolution (pad 1) over an h x w image: K = 9 * cin, k = tap * cin + c.  A k-tile never straddles
     // taps (cin % 32 == 0, checked on the host), so a tile is a plain K-major tile of the input shifted by the tap's
-    // (dy, dx); pixels whose tap falls outside the image are zeroed in store() through tapmask.
+    // (dy, dx); pixels whose tap falls outside the image are zeroed in store() through tapmask -- and load() fetches the
+    // unshifted pixel for them: a shifted address may lie before the image or up to w + 1 floats behind its last row, and
+    // neither the range check (the row offset travels in soffset, which the hardware does not check) nor anything else
+    // stops such a load.  Pixels past the operand are clamped as in init(): loaded, never stored.
     __device__ __forceinline__ void set_conv3x3(int x0, int h, int w, int tid) {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int idx = tid + j * kThreads;
-            const int x = x0 + idx % BX;                       // K-major item mapping: lanes walk x
+            const int x = min(x0 + idx % BX, h * w - 1);       // K-major item mapping: lanes walk x
             const int yy = x / w, xx = x % w;
             unsigned m = 0;
 #pragma unroll
@@ -116,14 +119,15 @@ struct Operand {
                 if (y2 >= 0 && y2 < h && x2 >= 0 && x2 < w) m |= 1u << t;
             }
             tapmask[j] = m;
-            voff[j] = x * 4;                                    // no clamping: out-of-range taps are masked / range-checked
+            voff[j] = x * 4;
         }
     }
 
     // Issue the raw loads of k-tile k0 (nothing is consumed here, so no wait is needed before the MFMAs).
     // K-major rows: tile_off = element offset of row k0 (tracked incrementally by the caller for grouped
-    // operands); rows past K are clamped to the last valid row and zeroed in store().
-    __device__ __forceinline__ void load(int k0, int tile_off, Regs& rg, int shift_bytes = 0) const {
+    // operands); rows past K are clamped to the last valid row and zeroed in store().  tap >= 0 (implicit 3x3 conv): the
+    // tap shift_bytes belongs to; an item whose tap lies outside the image loads its own pixel instead (see set_conv3x3).
+    __device__ __forceinline__ void load(int k0, int tile_off, Regs& rg, int shift_bytes = 0, int tap = -1) const {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             if (LAY == SF_LAYOUT_F16_K_MINOR) {
@@ -136,7 +140,7 @@ struct Operand {
             } else if (LAY == SF_LAYOUT_K_MAJOR) {
                 if (k0 + BK <= K) {
                     // interior k-tile (workgroup-uniform): one v_add per item, the row offsets are SGPR constants
-                    const int vo = voff[j] + tile_off * 4 + shift_bytes;
+                    const int vo = voff[j] + tile_off * 4 + ((tap >= 0 && !((tapmask[j] >> tap) & 1u)) ? 0 : shift_bytes);
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         if (kUniformKo) rg.v[j][i] = as_f(__builtin_amdgcn_raw_buffer_load_b32(rsrc, vo, rowc[j][i], 0));
@@ -243,7 +247,7 @@ struct OperandF16KMajor {
     }
     __device__ __forceinline__ void set_conv3x3(int, int, int, int) {}
 
-    __device__ __forceinline__ void load(int k0, int tile_off, Regs& rg, int = 0) const {
+    __device__ __forceinline__ void load(int k0, int tile_off, Regs& rg, int = 0, int = -1) const {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             if (k0 + BK <= K) {
@@ -290,7 +294,7 @@ struct OperandDma {
     struct Regs {};
     __device__ __forceinline__ void init(const void*, const void*, int64_t, int, int, int, int, int, int64_t, int) {}
     __device__ __forceinline__ void set_conv3x3(int, int, int, int) {}
-    __device__ __forceinline__ void load(int, int, Regs&, int = 0) const {}
+    __device__ __forceinline__ void load(int, int, Regs&, int = 0, int = -1) const {}
     template <bool kLo = false>
     __device__ __forceinline__ void store(int, _Float16*, _Float16*, Regs&, int = -1) const {}
 };
