@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 130
+#define SF_VERSION 131
 
 enum {
     SF_OK = 0,
@@ -871,6 +871,38 @@ int64_t sf_png_encode_ws_bytes(int n_images, int h, int w, int bpp);
 int sf_png_encode(const uint8_t* img, int64_t img_image_stride, int64_t img_row_stride, int n_images, int h, int w, int bpp,
                   int swap16, uint8_t* out, int64_t out_image_stride, int64_t* out_bytes, void* ws, int64_t ws_bytes, void* stream);
 int sf_flow_to_kitti16(const float* flow, uint16_t* out, int n, int h, int w, void* stream);
+
+/* ---- Spring .flo5 output: the HDF5 filters shuffle -> deflate of a batch of flow fields, chunk by chunk (flo5.flo5_file frames them) ---
+ * sf_flo5_encode: field i is two planes, element (ch, y, x) at flow + i field_stride + ch ch_stride + y row_stride + x (strides in
+ *   floats; an unpadded view of a padded field goes in as it is).  The HDF5 dataset is float32 [h][w][2] in chunks of
+ *   (rows_per_chunk, w, 2): nchunks = ceil(h / rows_per_chunk), chunk c starts at row c rows_per_chunk and has N = rows_per_chunk w 2
+ *   elements, element (y w + x) 2 + ch the BIT PATTERN of flow[ch][c rows_per_chunk + y][x] (NaN payloads, -0.0, infinities and
+ *   denormals pass unchanged), rows past h zero bits (libhdf5 stores edge chunks at full size).  HDF5's shuffle filter: byte j N + e
+ *   of the shuffled chunk is byte j (little-endian) of element e.  The slot out + (i nchunks + c) out_chunk_stride receives one
+ *   complete zlib stream and out_bytes[i nchunks + c] (device memory) its length:
+ *     `78 01`; for each byte plane j = 0 .. 3 in turn one block per segment of at most SF_FLO5_BLOCK_BYTES bytes (no block straddles two
+ *     planes), BFINAL on the last block of plane 3; the big-endian Adler-32 of the 4 N shuffled bytes.
+ *   A block is what sf_png_encode writes for a band (above): the same header fields, length-limited Huffman construction and canonical
+ *   codes, no repeat codes, the fixed 8 / 9-bit table wherever the dynamic table costs more.  tests/flo5_encode_cases.py restates the
+ *   format; the output equals that restatement byte for byte, and two runs are bitwise equal.
+ *   SF_FLO5_BLOCK_BYTES = 65536: see DESIGN.md 9.8 for the stream sizes at 16 / 64 / 256 KiB.
+ * sf_flo5_chunk_bound(rows_per_chunk, w): no stream is longer: 2 + ceil((nblk 1896 + 9 x 4 N) / 8) + 4 rounded up to a multiple of 4,
+ *   nblk = 4 ceil(N / SF_FLO5_BLOCK_BYTES); -1 for rows_per_chunk or w < 1 or 4 N >= 2^31.  The bytes of a slot between the stream's end
+ *   and the bound are unspecified (the call clears them itself: `out` need not be zeroed); nothing beyond the bound is written.
+ * sf_flo5_encode_ws_bytes: the workspace (the shuffled chunks, per-block tables); -1 for a shape or n sf_flo5_encode refuses.
+ * One memset and four launches (shuffle: a thread per 4 elements; tables: a workgroup per block; offsets: a thread per chunk; pack: a
+ *   workgroup per block, bits ORed in with vector atomics); dependencies between workgroups are launch boundaries and every trip
+ *   count depends on (n, h, w, rows_per_chunk) alone.  No host synchronisation.
+ *   SF_ERR_BAD_ARG before any launch for: null pointers, n outside 1 .. 65535, h, w or rows_per_chunk < 1, nchunks > 64 (the container
+ *   writes a single B-tree leaf), 4 N >= 2^31, row_stride < w, ch_stride < (h - 1) row_stride + w, field_stride < ch_stride +
+ *   (h - 1) row_stride + w, flow not 4-byte aligned, out_chunk_stride below the bound, out or out_chunk_stride not a multiple of 4,
+ *   out_bytes not 8-byte aligned, ws_bytes too small. */
+#define SF_FLO5_BLOCK_BYTES 65536
+int64_t sf_flo5_chunk_bound(int rows_per_chunk, int w);
+int64_t sf_flo5_encode_ws_bytes(int n, int h, int w, int rows_per_chunk);
+int sf_flo5_encode(const float* flow, int64_t field_stride, int64_t ch_stride, int64_t row_stride, int n, int h, int w,
+                   int rows_per_chunk, uint8_t* out, int64_t out_chunk_stride, int64_t* out_bytes, void* ws, int64_t ws_bytes,
+                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,9 @@ h5py's default):
 * data layout v3: compact, contiguous, or chunked through a version-1 B-tree (node type 1, any depth);
 * filter pipeline v1 / v2 with deflate (id 1) and shuffle (id 2); other filters raise.
 
-``write_flo5`` emits the same structures (one chunked, deflate-compressed dataset under the root group).
+``write_flo5`` emits the same structures (one chunked, deflate-compressed dataset under the root group).  The container framing is
+``flo5_file``, which takes the chunks already compressed: ``write_flo5`` hands it zlib's streams, ``flo5_gpu.write_batch`` the
+shuffled Huffman-only streams of ``ops.flo5_encode`` together with the ``shuffle`` filter in the pipeline message.
 Parity is pinned both ways against the real library (h5py 3.3.0 / HDF5 1.10.6 of the build container's conda interpreter,
 which is not this package's python): the reader decodes, bit for bit, the files under tests/golden/flo5 that h5py wrote with
 the reference's own call (tests/golden/make_flo5_golden.py), and files from ``write_flo5`` open in h5py with the same values,
@@ -59,17 +61,24 @@ def _float32_datatype() -> bytes:
     return head + props
 
 
-def write_flo5(path: str, flow: np.ndarray, compression_level: int = 5, rows_per_chunk: int = 0) -> None:
-    """flow [H, W, 2] -> HDF5 file with dataset 'flow' (float32, chunked, gzip), like frame_utils.py:46-47."""
-    flow = np.ascontiguousarray(flow, dtype="<f4")
-    if flow.ndim != 3 or flow.shape[2] != 2:
-        raise ValueError(f"writeFlo5File {path}: expected shape height x width x 2 but received {flow.shape}")
-    H, W, _ = flow.shape
-    if rows_per_chunk <= 0:                                 # <= 64 chunks: the chunk index is ONE B-tree leaf
-        rows_per_chunk = max(1, -(-H // 32))
+def flo5_file(chunks, h: int, w: int, rows_per_chunk: int, shuffle: bool = False, level: int = 5) -> bytes:
+    """The HDF5 file around the compressed chunks of a dataset 'flow' (float32 [h, w, 2], chunks (rows_per_chunk, w, 2)): chunks[c]
+    is the complete zlib stream of chunk c = rows c rows_per_chunk .. of the field, full-size (edge chunks zero padded, as libhdf5
+    stores them).  shuffle=False: the filter pipeline is `deflate` alone, the stream inflates to the chunk's bytes (write_flo5).
+    shuffle=True: the pipeline is `shuffle` (id 2, one client value: the element size 4), then `deflate`, and the stream inflates to
+    the byte-shuffled chunk -- byte j of element e at j N + e, N the chunk's element count -- which libhdf5 / h5py undo on reading
+    (ops.flo5_encode makes such streams on the GPU).  `level` is deflate's client value, what h5py reports as compression_opts; it
+    does not have to describe how the streams were made."""
+    H, W = int(h), int(w)
+    rows_per_chunk = int(rows_per_chunk)
+    if H < 1 or W < 1 or rows_per_chunk < 1:
+        raise ValueError(f"flo5_file: h = {h}, w = {w}, rows_per_chunk = {rows_per_chunk}")
     n_chunks = -(-H // rows_per_chunk)
     if n_chunks > 2 * CHUNK_K:
         raise ValueError("rows_per_chunk too small: more than 64 chunks")
+    blobs = [bytes(z) for z in chunks]
+    if len(blobs) != n_chunks:
+        raise ValueError(f"flo5_file: {len(blobs)} chunk streams for {n_chunks} chunks")
     cdims = (rows_per_chunk, W, 2)
 
     # ---- layout of the file: fixed-size metadata first, chunk data last
@@ -86,8 +95,12 @@ def write_flo5(path: str, flow: np.ndarray, compression_level: int = 5, rows_per
 
     dataspace = struct.pack("<BBB5x", 1, 3, 0) + struct.pack("<3Q", H, W, 2)
     fill = struct.pack("<BBBB", 2, 3, 2, 0)                  # v2: allocate incrementally, write fill if set, undefined
-    filters = (struct.pack("<BB6x", 1, 1) +                  # v1 pipeline, one filter
-               struct.pack("<HHHH", 1, 8, 1, 1) + b"deflate\0" + struct.pack("<I4x", int(compression_level)))
+    # v1 pipeline; a filter: id, name length, flags (1: optional), number of client values; the name; the values, padded to 8 bytes
+    deflate = struct.pack("<HHHH", 1, 8, 1, 1) + b"deflate\0" + struct.pack("<I4x", int(level))
+    if shuffle:
+        filters = struct.pack("<BB6x", 1, 2) + struct.pack("<HHHH", 2, 8, 1, 1) + b"shuffle\0" + struct.pack("<I4x", 4) + deflate
+    else:
+        filters = struct.pack("<BB6x", 1, 1) + deflate
     layout_size = 2 + 1 + 8 + 4 * 4
     dset_msgs_wo_layout = [_message(MSG_DATASPACE, dataspace), _message(MSG_DATATYPE, _float32_datatype(), 1),
                            _message(MSG_FILL, fill), _message(MSG_FILTERS, filters, 1)]
@@ -97,15 +110,9 @@ def write_flo5(path: str, flow: np.ndarray, compression_level: int = 5, rows_per
     cbtree_size = 24 + 2 * CHUNK_K * 8 + (2 * CHUNK_K + 1) * key_size
     off_chunks = off_cbtree + cbtree_size
 
-    # ---- chunks (edge chunks are stored full-size, zero padded, as libhdf5 does)
-    blobs, addrs = [], []
+    addrs = []
     pos = off_chunks
-    for c in range(n_chunks):
-        buf = np.zeros(cdims, "<f4")
-        rows = flow[c * rows_per_chunk:(c + 1) * rows_per_chunk]
-        buf[: rows.shape[0]] = rows
-        z = zlib.compress(buf.tobytes(), int(compression_level))
-        blobs.append(z)
+    for z in blobs:
         addrs.append(pos)
         pos += len(z)
     eof = pos
@@ -134,10 +141,32 @@ def write_flo5(path: str, flow: np.ndarray, compression_level: int = 5, rows_per
     snod = struct.pack("<4sBxH", b"SNOD", 1, 1) + struct.pack("<QQII16x", 8, off_dset, 0, 0)
     snod += b"\0" * (snod_size - len(snod))
 
+    data = b"".join((sup, root_hdr, gb, heap, heap_data, snod, dset_hdr, cb, *blobs))
+    assert len(data) == eof
+    return data
+
+
+def write_flo5(path: str, flow: np.ndarray, compression_level: int = 5, rows_per_chunk: int = 0) -> None:
+    """flow [H, W, 2] -> HDF5 file with dataset 'flow' (float32, chunked, gzip), like frame_utils.py:46-47."""
+    flow = np.ascontiguousarray(flow, dtype="<f4")
+    if flow.ndim != 3 or flow.shape[2] != 2:
+        raise ValueError(f"writeFlo5File {path}: expected shape height x width x 2 but received {flow.shape}")
+    H, W, _ = flow.shape
+    if rows_per_chunk <= 0:                                 # <= 64 chunks: the chunk index is ONE B-tree leaf
+        rows_per_chunk = max(1, -(-H // 32))
+    n_chunks = -(-H // rows_per_chunk)
+    if n_chunks > 2 * CHUNK_K:
+        raise ValueError("rows_per_chunk too small: more than 64 chunks")
+    # ---- chunks (edge chunks are stored full-size, zero padded, as libhdf5 does)
+    blobs = []
+    for c in range(n_chunks):
+        buf = np.zeros((rows_per_chunk, W, 2), "<f4")
+        rows = flow[c * rows_per_chunk:(c + 1) * rows_per_chunk]
+        buf[: rows.shape[0]] = rows
+        blobs.append(zlib.compress(buf.tobytes(), int(compression_level)))
+    data = flo5_file(blobs, H, W, rows_per_chunk, shuffle=False, level=int(compression_level))
     with open(path, "wb") as f:
-        for part in (sup, root_hdr, gb, heap, heap_data, snod, dset_hdr, cb, *blobs):
-            f.write(part)
-        assert f.tell() == eof
+        f.write(data)
 
 
 # ------------------------------------------------------------------------------------------------------------

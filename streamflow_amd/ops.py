@@ -1502,6 +1502,43 @@ def flow_to_kitti16(flows: torch.Tensor) -> torch.Tensor:
     return out
 
 
+@on_tensor_device
+def flo5_encode(flows: torch.Tensor, rows_per_chunk: int = 0):
+    """The compressed HDF5 chunks of Spring .flo5 files for a batch of device flows (sf_flo5_encode: byte shuffle and Huffman-only
+    deflate, csrc/flo5_encode.hip; the host half is flo5.flo5_file with shuffle=True): flows fp32 [n, 2, H, W] on the GPU, the
+    samples of a row contiguous, any row / channel / field strides that do not overlap (an unpadded view of the model's padded output
+    goes in without a copy).  rows_per_chunk = 0: flo5.write_flo5's rule, ceil(H / 32).  Returns (streams uint8 [n, nchunks,
+    sf_flo5_chunk_bound], lengths int64 [n, nchunks]) on the same GPU: chunk c of field i is streams[i, c, :lengths[i, c]], the bytes
+    behind it are unspecified.  Enqueued on the current stream, no synchronisation."""
+    if not isinstance(flows, torch.Tensor) or not flows.is_cuda:
+        raise RuntimeError(f"flo5_encode: flows must be on the GPU (got {getattr(flows, 'device', type(flows).__name__)}); "
+                           "there is no CPU fallback -- flo5.write_flo5 is the host-side path")
+    if flows.dtype != torch.float32 or flows.dim() != 4 or flows.shape[1] != 2 or flows.numel() == 0:
+        raise RuntimeError(f"flo5_encode: expected float32 [n, 2, H, W], got {flows.dtype} {tuple(flows.shape)}")
+    n, _, h, w = (int(v) for v in flows.shape)
+    rpc = int(rows_per_chunk)
+    if rpc < 0:
+        raise RuntimeError(f"flo5_encode: rows_per_chunk = {rows_per_chunk}")
+    if rpc == 0:
+        rpc = max(1, -(-h // 32))
+    plane = (h - 1) * flows.stride(2) + w
+    if flows.stride(3) != 1 or flows.stride(2) < w or flows.stride(1) < plane or (n > 1 and flows.stride(0) < flows.stride(1) + plane):
+        raise RuntimeError(f"flo5_encode: the samples of a row must be contiguous and rows / channels / fields must not overlap "
+                           f"(strides {flows.stride()})")
+    lib = _lib.load()
+    bound, ws_bytes = lib.sf_flo5_chunk_bound(rpc, w), lib.sf_flo5_encode_ws_bytes(n, h, w, rpc)
+    if bound < 0 or ws_bytes < 0:
+        raise RuntimeError(f"flo5_encode: n = {n}, h = {h}, w = {w}, rows_per_chunk = {rpc} is outside what sf_flo5_encode takes")
+    nchunks = -(-h // rpc)
+    streams = torch.empty(n, nchunks, bound, dtype=torch.uint8, device=flows.device)
+    lengths = torch.empty(n, nchunks, dtype=torch.int64, device=flows.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=flows.device)
+    field_stride = flows.stride(0) if n > 1 else flows.stride(1) + plane
+    _lib.check(lib.sf_flo5_encode(flows.data_ptr(), field_stride, flows.stride(1), flows.stride(2), n, h, w, rpc, streams.data_ptr(), bound,
+                                  lengths.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream()), "sf_flo5_encode")
+    return streams, lengths
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None

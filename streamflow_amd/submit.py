@@ -12,7 +12,8 @@
   ``vis_path/flow/000NNN_10.png`` when `vis_path` is given (the reference always writes ``vis_kitti2/`` into the working directory).
 * ``create_spring_submission_mf(args, model, iters, output_path, nframes)`` -- evaluate_mf.py:25-48 over
   ``args.spring_root/test/<scene>/frame_{left,right}/*.png``: forward and backward clips of every scene and camera, each flow as
-  ``output_path/<scene>/flow_<FW|BW>_<cam>/flow_<FW|BW>_<cam>_%04d.flo5`` (flo5.write_flo5, gzip level 5); no colour images.
+  ``output_path/<scene>/flow_<FW|BW>_<cam>/flow_<FW|BW>_<cam>_%04d.flo5`` (flo5.write_flo5, gzip level 5; ``flo5_encode="gpu"``:
+  flo5_gpu.write_batch, compressed on the device); no colour images.
 
 ``model`` is the reference's test-mode call (see evaluate.py); the tree walks, the frame reader and the per-clip model call are
 datasets.py's, shared with evaluate.py.  The colour images of one clip are made on the device by ONE
@@ -106,14 +107,18 @@ def create_sintel_submission_mf_warmup(args, model: Callable, iters: int, output
 
 @torch.no_grad()
 def create_spring_submission_mf(args, model: Callable, iters: int, output_path: str = "sintel_submission", nframes: int = 4,
-                                device: Optional[torch.device] = None) -> None:
+                                device: Optional[torch.device] = None, flo5_encode: str = "host") -> None:
     """Create the submission tree for the Spring leaderboard (evaluate_mf.py:25-48 over SpringSubmission, mf_datasets.py:47-97):
     every scene of ``args.spring_root/test`` (sorted), both cameras, the forward clips and then the backward clips (the frames
     reversed), every clip from a cold start on sintel_clip_schedule.  Each pair whose frame id is not -1 is written with
     flo5.write_flo5 (gzip level 5, the reference's) as ``output_path/<scene>/flow_<FW|BW>_<cam>/flow_<FW|BW>_<cam>_%04d.flo5`` with
     the 1-based id j + 1 forward and n - j backward (j: the source frame's index in the forward or reversed list).  As in the
-    reference there are no colour images, and the default output_path is the reference's 'sintel_submission'."""
+    reference there are no colour images, and the default output_path is the reference's 'sintel_submission'.
+    flo5_encode="gpu": the kept pairs of a clip are compressed on the device and written by ONE flo5_gpu.write_batch call (the same
+    dataset bit for bit; another filter pipeline, shuffle + Huffman-only deflate, which h5py undoes on reading)."""
     from . import flo5
+    if flo5_encode not in ("host", "gpu"):
+        raise ValueError(f"flo5_encode must be 'host' or 'gpu', got {flo5_encode!r}")
     _eval_mode(model)
     dev = device or model_device(model, torch.device("cpu"))
     for scene, cam, direction, order, n, schedule in spring_clips(args.spring_root, "test", nframes):
@@ -121,6 +126,14 @@ def create_spring_submission_mf(args, model: Callable, iters: int, output_path: 
         for first, ids in schedule:
             flows = run_clip(model, order[first:first + nframes], dev, iters)
             assert len(flows) == len(ids) - 1
+            if flo5_encode == "gpu":
+                from . import flo5_gpu
+                keep = [k for k, j in enumerate(ids[:-1]) if j != -1]
+                if keep:                                    # one field: the unpadded view itself; more: one batch tensor
+                    fields = [flows[k].float() for k in keep]
+                    flo5_gpu.write_batch(fields[0][None] if len(fields) == 1 else torch.stack(fields),
+                                         [os.path.join(output_path, scene, spring_flow_file(direction, cam, n, ids[k])) for k in keep])
+                continue
             for k, j in enumerate(ids[:-1]):
                 if j != -1:
                     flo5.write_flo5(os.path.join(output_path, scene, spring_flow_file(direction, cam, n, j)),
