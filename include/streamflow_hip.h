@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 131
+#define SF_VERSION 132
 
 enum {
     SF_OK = 0,
@@ -903,6 +903,51 @@ int64_t sf_flo5_encode_ws_bytes(int n, int h, int w, int rows_per_chunk);
 int sf_flo5_encode(const float* flow, int64_t field_stride, int64_t ch_stride, int64_t row_stride, int n, int h, int w,
                    int rows_per_chunk, uint8_t* out, int64_t out_chunk_stride, int64_t* out_bytes, void* ws, int64_t ws_bytes,
                    void* stream);
+
+/* ---- Spring .flo5 input: a batch of zlib streams inflated on the device, and the inflated chunks put together (csrc/flo5_decode.hip) ----
+ * sf_inflate: n independent zlib streams (RFC 1950 / 1951) -> bytes; generic, it knows nothing of HDF5.  desc (device memory) holds
+ *   SF_INFLATE_DESC_WORDS int64 per stream: in_off, in_len, out_off, out_len, flags.  The stream is in[in_off .. in_off + in_len) (any
+ *   alignment; bytes behind the stream's end are ignored) and must inflate to EXACTLY out_len bytes, written to out[out_off ..
+ *   out_off + out_len) (out_len < 2^31; slots of different streams must not overlap).  flags & SF_INFLATE_STORED: no stream, the in_len
+ *   bytes are the data and are copied (an HDF5 chunk whose filter mask skips deflate).  One wave per stream; every block type, repeat
+ *   codes, codes up to 15 bits, distances up to 32 768, overlapping matches, any number of blocks; the zlib header and the Adler-32
+ *   trailer are verified, a preset dictionary is refused.  status[i] (device memory) receives 0 or one of SF_INFLATE_* below; a failed
+ *   stream leaves unspecified bytes inside its own slot and nothing anywhere else.  For ANY input bytes every read stays inside the
+ *   stream's input range and every write inside its slot, and the kernel ends within 8 in_len + out_len decode steps (DESIGN.md 9.9;
+ *   the decoder core, csrc/inflate_core.h, runs under the host sanitizers as csrc/host/inflate_host_main.cpp).  Two runs are bitwise
+ *   equal.  No workspace, one launch, no host synchronisation.
+ *   SF_ERR_BAD_ARG before the launch for: null pointers, n outside 1 .. SF_INFLATE_MAX_STREAMS, negative in_bytes / out_bytes, desc not
+ *   8-byte or status not 4-byte aligned.  What desc holds is checked on the device: SF_INFLATE_BAD_SLOT.
+ * sf_flo5_assemble: the chunks of n files of ONE geometry -> out [n][h][w][2] float32 bit patterns (read_flo5's array).  The dataset is
+ *   (h, w, 2) little-endian float32 in chunks of (ch, cw, cc), cc 1 or 2; slot s is the chunk_stride bytes at chunks + s chunk_stride,
+ *   of which the first 4 ch cw cc are one inflated chunk (byte-shuffled -- byte j of element e at j N + e -- when shuffle != 0).
+ *   grid (device memory, int32 [n][ceil(h / ch)][ceil(w / cw)][2 / cc]) names the slot of every chunk, or -1 (any value outside
+ *   0 .. n_slots - 1) for a chunk the file does not store: its elements are 0.0, the fill value.  Edge chunks lose their padding.
+ *   A thread per pixel; one launch.  SF_ERR_BAD_ARG for: null pointers, n or h outside 1 .. 65535, w, ch, cw < 1, cc not 1 or 2,
+ *   4 ch cw cc >= 2^31, n_slots < 0, chunk_stride below 4 ch cw cc or no multiple of 4, chunks / grid not 4-byte or out not 8-byte
+ *   aligned. */
+#define SF_INFLATE_DESC_WORDS 5
+#define SF_INFLATE_STORED 1
+#define SF_INFLATE_MAX_STREAMS 16777216
+enum {
+    SF_INFLATE_OK = 0,
+    SF_INFLATE_BAD_HEADER = 1,       /* CM != 8, CINFO > 7 or the check bits */
+    SF_INFLATE_TRUNCATED = 2,        /* the input ends inside the stream */
+    SF_INFLATE_BAD_BLOCK_TYPE = 3,   /* BTYPE 3 */
+    SF_INFLATE_BAD_CODE_LENGTHS = 4, /* over-subscribed or incomplete set, HLIT / HDIST out of range, bad repeat, no end-of-block code */
+    SF_INFLATE_BAD_SYMBOL = 5,       /* bits that are no code; literal/length 286 / 287; distance 30 / 31 */
+    SF_INFLATE_BAD_DISTANCE = 6,     /* a distance before the start of the output */
+    SF_INFLATE_OUTPUT_LONG = 7,      /* more output than out_len */
+    SF_INFLATE_OUTPUT_SHORT = 8,     /* less output than out_len */
+    SF_INFLATE_BAD_ADLER = 9,        /* the trailer does not match the output */
+    SF_INFLATE_BAD_STORED_LEN = 10,  /* a stored block whose NLEN is not ~LEN */
+    SF_INFLATE_PRESET_DICT = 11,     /* FDICT set */
+    SF_INFLATE_BAD_SLOT = 12         /* the stream's input or output range lies outside the buffers, or out_len >= 2^31 */
+};
+int sf_inflate(const uint8_t* in, int64_t in_bytes, const int64_t* desc, int n, uint8_t* out, int64_t out_bytes, int32_t* status,
+               void* stream);
+int sf_flo5_assemble(const uint8_t* chunks, int64_t chunk_stride, int n_slots, const int32_t* grid, int n, int h, int w, int ch, int cw,
+                     int cc, int shuffle, float* out, void* stream);
 
 #ifdef __cplusplus
 }

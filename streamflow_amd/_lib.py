@@ -192,6 +192,8 @@ SIGNATURES = {
     "sf_flo5_chunk_bound": (_i64, [_i, _i]),
     "sf_flo5_encode_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "sf_flo5_encode": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sf_inflate": (_i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp]),
+    "sf_flo5_assemble": (_i, [_vp, _i64, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -217,7 +219,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 131:
+    if lib.sf_version() < 132:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -22,9 +22,9 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libstreamflow_hip.so")
 ASAN_OBJ = os.path.join(CSRC, "build_asan")
 ASAN_LIB = os.path.join(HERE, "libstreamflow_hip_asan.so")
-SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip", "flow_score_batch.hip", "video_io.hip", "png_unfilter.hip", "png_encode.hip", "flo5_encode.hip"]
+SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip", "flow_score_batch.hip", "video_io.hip", "png_unfilter.hip", "png_encode.hip", "flo5_encode.hip", "flo5_decode.hip"]
 HEADERS = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "weight_ring.h"), os.path.join(CSRC, "gemm_epilogue.h"),
-           os.path.join(CSRC, "split_operand.h"), os.path.join(CSRC, "huff_deflate.h"), os.path.join(HERE, "..", "include", "streamflow_hip.h")]
+           os.path.join(CSRC, "split_operand.h"), os.path.join(CSRC, "huff_deflate.h"), os.path.join(CSRC, "inflate_core.h"), os.path.join(HERE, "..", "include", "streamflow_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function",
          # per-kernel registers / scratch / occupancy as compiler remarks: kept next to every object (<name>.res) and checked
@@ -36,7 +36,8 @@ HOT_KERNELS = ("gemm_bstat", "ffn_pair_kernel", "sk_tail_kernel", "gma_flash_pip
                "corr_lookup_blocked_kernel", "corr_build_blocked_kernel", "corr_lookup_blocked32_kernel", "corr_build_blocked32_kernel", "temporal_attn_kernel", "layernorm_cm_split_kernel",
                "flash_pack_v_kernel", "flow_score_kernel", "flow_score_batch_kernel", "frames_to_clips_kernel", "clips_to_flows_kernel", "png_unfilter_kernel",
                "png_filter_kernel", "png_table_kernel", "png_offsets_kernel", "png_pack_kernel", "flow_to_kitti16_kernel",
-               "flo5_shuffle_kernel", "flo5_table_kernel", "flo5_offsets_kernel", "flo5_pack_kernel")
+               "flo5_shuffle_kernel", "flo5_table_kernel", "flo5_offsets_kernel", "flo5_pack_kernel",
+               "inflate_kernel", "flo5_assemble_kernel")
 
 
 def hipcc() -> str:

@@ -68,6 +68,11 @@ def _check_png_decode(png_decode: str) -> None:
         raise ValueError(f"png_decode {png_decode!r} ('host' or 'gpu')")
 
 
+def _check_flo5_decode(flo5_decode: str) -> None:
+    if flo5_decode not in ("host", "gpu"):
+        raise ValueError(f"flo5_decode must be 'host' or 'gpu' (got {flo5_decode!r})")
+
+
 def _need_gpu(what: str, dev: torch.device) -> torch.device:
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError(f"{what}: clips_per_step > 1 runs on the GPU (device {dev}, GPU available: {torch.cuda.is_available()}); "
@@ -295,7 +300,7 @@ def _kitti_batched(model: Callable, iters: int, image_root: str, flow_root: str,
 # ---- Spring (evaluate_mf.py:50-102, core/mf_datasets.py:99-213) ---------------------------------------------------------------
 @torch.no_grad()
 def spring_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", nframes: int = 3, device: Optional[torch.device] = None,
-                  scenes: Optional[Sequence[str]] = ("0041",)) -> Dict[str, float]:
+                  scenes: Optional[Sequence[str]] = ("0041",), flo5_decode: str = "host") -> Dict[str, float]:
     """The Spring validation of the reference (validate_spring_mf over SpringEval) as a dictionary: 'epe', '1px', '3px', '5px',
     'spring_1px', 'spring_1px_s0_10', 'spring_1px_s10_40', 'spring_1px_s40' (what the reference prints), plus 'epe_valid',
     'pixels', 'valid_pixels' and 'pairs'.
@@ -306,9 +311,16 @@ def spring_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
     skipped.  Flows on the GPU are scored where they are by ops.flow_score into one device accumulator (one copy to the host at the end);
     host flows (a CPU model) by scoring.score_host, with the same arithmetic (scoring.py states how both relate to the reference).
     Reference quirks kept: only scene 0041 by default (the hard-coded train / val split, mf_datasets.py:117; scenes=None scores
-    every scene); the dataset's |flow| < 1000 valid maps are not used; 'epe' is NaN as soon as one ground-truth pixel is NaN."""
-    from . import flo5, ops, scoring
+    every scene); the dataset's |flow| < 1000 valid maps are not used; 'epe' is NaN as soon as one ground-truth pixel is NaN.
+    flo5_decode="gpu": the ground truth of a clip's scored pairs is read by ONE flo5_gpu.read_batch call (chunks inflated and put
+    together on the device, csrc/flo5_decode.hip) and handed to ops.flow_score as it is: the same bits as flo5.read_flo5's array, so
+    the report is the host run's, key for key.  It needs the flows on the GPU; "host" (the default) is flo5.read_flo5 + an upload."""
+    from . import flo5, flo5_gpu, ops, scoring
+    _check_flo5_decode(flo5_decode)
     dev = device or model_device(model, torch.device("cpu"))
+    if flo5_decode == "gpu" and (dev.type != "cuda" or not torch.cuda.is_available()):
+        raise RuntimeError(f"spring_report: flo5_decode='gpu' decodes the ground truth on the GPU (device {dev}, GPU available: "
+                           f"{torch.cuda.is_available()}); there is no CPU fallback -- flo5_decode='host' is the host-side path")
     train = os.path.join(root, "train")
     acc_host = np.zeros(scoring.LEN, np.float64)
     acc_dev = {}
@@ -317,16 +329,28 @@ def spring_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
     for scene, cam, direction, order, n, schedule in spring_clips(root, "train", nframes, only=scenes):
         for first, ids in schedule:
             flows = run_clip(model, order[first:first + nframes], dev, iters)
-            for k in range(nframes - 1):
-                if ids[k] == -1:
-                    continue
-                gt = flo5.read_flo5(os.path.join(train, scene, spring_flow_file(direction, cam, n, first + k)))
+            scored = [k for k in range(nframes - 1) if ids[k] != -1]
+            files = {k: os.path.join(train, scene, spring_flow_file(direction, cam, n, first + k)) for k in scored}
+            gts = {}
+            if flo5_decode == "gpu" and scored:
+                if not flows[scored[0]].is_cuda:
+                    raise RuntimeError("spring_report: flo5_decode='gpu' needs the model's flows on the GPU; there is no CPU fallback")
+                gts = dict(zip(scored, flo5_gpu.read_batch([files[k] for k in scored], flows[scored[0]].device)))
+            for k in scored:
                 pred = flows[k]
+                if k in gts:
+                    gt = gts[k]
+                    if gt.dtype != torch.float32:
+                        gt = gt.float()
+                else:
+                    gt = flo5.read_flo5(files[k])
                 if pred.is_cuda:
                     acc = acc_dev.get(pred.device)
                     if acc is None:
                         acc = acc_dev[pred.device] = torch.zeros(scoring.LEN, dtype=torch.float64, device=pred.device)
-                    ops.flow_score(pred.float(), torch.from_numpy(np.ascontiguousarray(gt, np.float32)).to(pred.device), acc, step)
+                    if not isinstance(gt, torch.Tensor):
+                        gt = torch.from_numpy(np.ascontiguousarray(gt, np.float32)).to(pred.device)
+                    ops.flow_score(pred.float(), gt, acc, step)
                 else:
                     scoring.score_host(pred.float().numpy(), gt, acc_host, step)
                 pairs += 1
@@ -344,12 +368,15 @@ def spring_report(model: Callable, iters: int = 6, root: str = "/data/Sintel", n
 
 @torch.no_grad()
 def validate_spring_mf(model: Callable, iters: int = 6, root: str = "/data/Sintel", tqdm_miniters: int = 1, nframes: int = 3,
-                       split: bool = False, device: Optional[torch.device] = None, scenes: Optional[Sequence[str]] = ("0041",)) -> float:
+                       split: bool = False, device: Optional[torch.device] = None, scenes: Optional[Sequence[str]] = ("0041",),
+                       flo5_decode: str = "host") -> float:
     """The reference's return value: the mean EPE over every scored pixel (evaluate_mf.py:50-102).  `split` and `tqdm_miniters`
-    are accepted and ignored (the reference's SpringEval applies its 0041 split whatever `split` says; there is no progress bar)."""
+    are accepted and ignored (the reference's SpringEval applies its 0041 split whatever `split` says; there is no progress bar).
+    flo5_decode: as for spring_report."""
+    _check_flo5_decode(flo5_decode)
     if hasattr(model, "eval"):
         model.eval()
-    return spring_report(model, iters, root, nframes, device=device, scenes=scenes)["epe"]
+    return spring_report(model, iters, root, nframes, device=device, scenes=scenes, flo5_decode=flo5_decode)["epe"]
 
 
 # ---- tiled inference (evaluate_mf.py:858-1053) ------------------------------------------------------------------------------
@@ -480,6 +507,8 @@ def main(argv=None) -> int:
                     help="clips per model call (sintel, sintel_occ, kitti; 1 = the reference's per-clip loop scored on the host)")
     ap.add_argument("--png-decode", default="gpu", choices=("gpu", "host"),
                     help="where PNG rows are unfiltered when clips-per-step > 1 (the same bytes either way; 1 always decodes on the host)")
+    ap.add_argument("--flo5-decode", default="gpu", choices=("gpu", "host"),
+                    help="where Spring's .flo5 ground truth is inflated and put together (--dataset spring; the same bits either way)")
     ap.add_argument("--preset", default=None, help="arithmetic preset (streamflow_amd.presets); default: fp32_class")
     a = ap.parse_args(argv)
     png_decode = a.png_decode if a.clips_per_step > 1 else "host"
@@ -494,7 +523,7 @@ def main(argv=None) -> int:
     elif a.dataset == "kitti_tile":
         res = validate_kitti_mf_tile(model, iters=a.iters, multi_root=a.root, nframes=a.T)
     else:
-        res = {"spring": validate_spring_mf(model, iters=a.iters, root=a.root, nframes=a.T)}
+        res = {"spring": validate_spring_mf(model, iters=a.iters, root=a.root, nframes=a.T, flo5_decode=a.flo5_decode)}
     print(" ".join("%s: %f" % (k, v) for k, v in res.items()))
     return 0
 

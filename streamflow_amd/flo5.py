@@ -18,6 +18,9 @@ Parity is pinned both ways against the real library (h5py 3.3.0 / HDF5 1.10.6 of
 which is not this package's python): the reader decodes, bit for bit, the files under tests/golden/flo5 that h5py wrote with
 the reference's own call (tests/golden/make_flo5_golden.py), and files from ``write_flo5`` open in h5py with the same values,
 gzip level 5 (tests/test_flow_io_cpu.py); plus the round trips and byte-level structure checks.
+
+``chunk_table`` is the reader's walk without the decoding: the index flo5_gpu.read_batch uploads from, for the chunks to be inflated
+and put together on the GPU (csrc/flo5_decode.hip).
 """
 from __future__ import annotations
 
@@ -317,6 +320,54 @@ class _File:
             sl = tuple(slice(o, min(o + c, s)) for o, c, s in zip(offs, cshape, out.shape))
             out[sl] = chunk[tuple(slice(0, s.stop - s.start) for s in sl)]
 
+    # -- the index alone ------------------------------------------------------------------------------------------
+    def chunk_index(self, header_addr: int) -> dict:
+        """dataset()'s walk without decoding anything: see chunk_table."""
+        msgs = self.messages(header_addr)
+        get = lambda t: next((b for mt, b in msgs if mt == t), None)
+        sp, dt, lay, flt = get(MSG_DATASPACE), get(MSG_DATATYPE), get(MSG_LAYOUT), get(MSG_FILTERS)
+        if sp is None or dt is None or lay is None:
+            raise IOError(f"{self.path}: dataset header lacks dataspace / datatype / layout")
+        sver, rank = sp[0], sp[1]
+        shape = tuple(int(v) for v in struct.unpack_from(f"<{rank}Q", sp, 8 if sver == 1 else 4))
+        dtype = self._dtype(dt)
+        filters = self._filters(flt) if flt is not None else []
+        lver, lclass = lay[0], lay[1]
+        if lver != 3:
+            raise IOError(f"{self.path}: data layout version {lver} is not supported")
+        if lclass not in (0, 1, 2):
+            raise IOError(f"{self.path}: unknown layout class {lclass}")
+        table = {"path": self.path, "shape": shape, "dtype": dtype, "filters": filters, "chunked": lclass == 2, "chunk_shape": None,
+                 "chunks": [], "data": self.d}
+        if lclass != 2:
+            return table
+        nd = lay[2]
+        btree = struct.unpack_from("<Q", lay, 3)[0]
+        cdims = struct.unpack_from(f"<{nd}I", lay, 11)
+        if nd != rank + 1 or cdims[-1] != dtype.itemsize:
+            raise IOError(f"{self.path}: chunk dimensionality {nd} does not match rank {rank}")
+        table["chunk_shape"] = tuple(int(v) for v in cdims[:-1])
+        if btree != UNDEF:
+            self._chunk_entries(btree, nd, table["chunks"])
+        return table
+
+    def _chunk_entries(self, addr, nd, out) -> None:
+        sig, ntype, level, used = struct.unpack_from("<4sBBH", self.at(addr, 8))
+        if sig != b"TREE" or ntype != 1:
+            raise IOError(f"{self.path}: bad chunk B-tree node")
+        ksz = 8 + 8 * nd
+        body = self.at(addr + 24, used * (ksz + 8) + ksz)
+        for i in range(used):
+            p = i * (ksz + 8)
+            nbytes, mask = struct.unpack_from("<II", body, p)
+            offs = struct.unpack_from(f"<{nd}Q", body, p + 8)[:-1]
+            child = struct.unpack_from("<Q", body, p + ksz)[0]
+            if level > 0:
+                self._chunk_entries(child, nd, out)
+                continue
+            self.at(child, nbytes)                                # the reader's bounds check, with its message
+            out.append((tuple(int(o) for o in offs), self.base + child, int(nbytes), int(mask)))
+
     def _dtype(self, dt: bytes) -> np.dtype:
         cls, b0 = dt[0] & 0x0F, dt[1]
         size = struct.unpack_from("<I", dt, 4)[0]
@@ -351,6 +402,27 @@ def read_hdf5_dataset(path: str, name: str) -> np.ndarray:
     if name not in entries:
         raise IOError(f"File {path} does not have a '{name}' key. Is this a valid flo5 file?")
     return hf.dataset(entries[name])
+
+
+def chunk_table(path_or_bytes, name: str = "flow") -> dict:
+    """The index of dataset `name` of an HDF5 file (a path, or the file's bytes) without decoding anything -- the walk of
+    read_hdf5_dataset, with its error messages for the same malformed files:
+        {"path", "shape", "dtype", "filters": [filter ids in pipeline order], "chunked": bool, "chunk_shape": tuple or None,
+         "chunks": [(element offsets, byte address in `data`, nbytes, filter mask)] in B-tree order, "data": the file's bytes}
+    A chunk's stored bytes are data[address : address + nbytes]; bit k of its filter mask set means pipeline stage k was skipped for
+    it.  Compact and contiguous datasets have chunked = False and no chunks (read them with read_hdf5_dataset).  This is what
+    flo5_gpu.read_batch uploads from; `_File.dataset` is the same walk with the decoding in it."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data, path = bytes(path_or_bytes), "<bytes>"
+    else:
+        path = str(path_or_bytes)
+        with open(path, "rb") as f:
+            data = f.read()
+    hf = _File(data, path)
+    entries = hf.group_entries(hf.root_header)
+    if name not in entries:
+        raise IOError(f"File {path} does not have a '{name}' key. Is this a valid flo5 file?")
+    return hf.chunk_index(entries[name])
 
 
 def read_flo5(path: str) -> np.ndarray:

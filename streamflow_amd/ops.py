@@ -1539,6 +1539,68 @@ def flo5_encode(flows: torch.Tensor, rows_per_chunk: int = 0):
     return streams, lengths
 
 
+INFLATE_DESC_WORDS, INFLATE_STORED = 5, 1
+INFLATE_STATUS = ("ok", "bad zlib header", "truncated input", "block type 3", "bad code-length set", "invalid symbol",
+                  "distance before the start of the output", "output longer than expected", "output shorter than expected",
+                  "Adler-32 mismatch", "stored block LEN / NLEN mismatch", "preset dictionary", "stream outside the buffers")
+
+
+@on_tensor_device
+def inflate(comp: torch.Tensor, desc: torch.Tensor, out: torch.Tensor):
+    """A batch of zlib streams inflated on the GPU (sf_inflate, csrc/flo5_decode.hip: one wave per stream).  comp uint8 [B], the
+    compressed bytes; desc int64 [n, 5] = (in_off, in_len, out_off, out_len, flags) per stream, flags & 1: the bytes are stored as
+    they are and are copied; out uint8 [O], written inside the streams' slots only.  All three on the same GPU.  Returns status
+    int32 [n] on that GPU: 0, or an index into INFLATE_STATUS (include/streamflow_hip.h SF_INFLATE_*).  Enqueued on the current
+    stream, no synchronisation: reading the status is the caller's."""
+    for name, t, dt in (("comp", comp, torch.uint8), ("desc", desc, torch.int64), ("out", out, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"inflate: {name} must be on the GPU (got {getattr(t, 'device', type(t).__name__)}); "
+                               "there is no CPU fallback -- zlib.decompress is the host-side path")
+        if t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"inflate: {name} must be a contiguous {dt} tensor, got {t.dtype} {tuple(t.shape)}")
+    if comp.dim() != 1 or out.dim() != 1 or desc.dim() != 2 or desc.shape[1] != INFLATE_DESC_WORDS or desc.shape[0] < 1:
+        raise RuntimeError(f"inflate: expected comp [B], desc [n >= 1, {INFLATE_DESC_WORDS}], out [O]; got {tuple(comp.shape)}, "
+                           f"{tuple(desc.shape)}, {tuple(out.shape)}")
+    if comp.device != desc.device or comp.device != out.device:
+        raise RuntimeError(f"inflate: comp, desc and out must share a device ({comp.device}, {desc.device}, {out.device})")
+    n = int(desc.shape[0])
+    status = torch.empty(n, dtype=torch.int32, device=comp.device)
+    lib = _lib.load()
+    # an empty tensor has no storage to point at: any non-null, never dereferenced address stands for it
+    ptr = lambda t: t.data_ptr() or status.data_ptr()
+    _lib.check(lib.sf_inflate(ptr(comp), comp.numel(), desc.data_ptr(), n, ptr(out), out.numel(), status.data_ptr(), _lib.stream()),
+               "sf_inflate")
+    return status
+
+
+@on_tensor_device
+def flo5_assemble(chunks: torch.Tensor, grid: torch.Tensor, h: int, w: int, chunk_shape, shuffle: bool) -> torch.Tensor:
+    """Inflated .flo5 chunks -> the datasets (sf_flo5_assemble).  chunks uint8 [n_slots, chunk_stride] on the GPU, a slot's first
+    4 ch cw cc bytes one inflated chunk of a float32 (h, w, 2) dataset in chunks of chunk_shape = (ch, cw, cc), cc 1 or 2,
+    byte-shuffled when `shuffle`; grid int32 [n, ceil(h / ch), ceil(w / cw), 2 // cc]: the slot of every chunk of every file, -1
+    for a chunk the file does not store (0.0).  Returns float32 [n, h, w, 2], file i bit for bit flo5.read_flo5's array."""
+    for name, t, dt in (("chunks", chunks, torch.uint8), ("grid", grid, torch.int32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"flo5_assemble: {name} must be on the GPU (got {getattr(t, 'device', type(t).__name__)}); "
+                               "there is no CPU fallback -- flo5.read_flo5 is the host-side path")
+        if t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"flo5_assemble: {name} must be a contiguous {dt} tensor, got {t.dtype} {tuple(t.shape)}")
+    ch, cw, cc = (int(v) for v in chunk_shape)
+    h, w = int(h), int(w)
+    if h < 1 or w < 1 or ch < 1 or cw < 1 or cc not in (1, 2):
+        raise RuntimeError(f"flo5_assemble: h = {h}, w = {w}, chunk_shape = {(ch, cw, cc)} (cc must be 1 or 2)")
+    want = (-(-h // ch), -(-w // cw), 2 // cc)
+    if grid.dim() != 4 or tuple(grid.shape[1:]) != want or grid.shape[0] < 1 or chunks.dim() != 2 or chunks.device != grid.device:
+        raise RuntimeError(f"flo5_assemble: expected grid [n, {want[0]}, {want[1]}, {want[2]}] and chunks [n_slots, stride] on one "
+                           f"device, got {tuple(grid.shape)} and {tuple(chunks.shape)}")
+    n = int(grid.shape[0])
+    out = torch.empty(n, h, w, 2, dtype=torch.float32, device=chunks.device)
+    lib = _lib.load()
+    _lib.check(lib.sf_flo5_assemble(chunks.data_ptr() or out.data_ptr(), int(chunks.shape[1]), int(chunks.shape[0]), grid.data_ptr(), n, h, w,
+                                    ch, cw, cc, 1 if shuffle else 0, out.data_ptr(), _lib.stream()), "sf_flo5_assemble")
+    return out
+
+
 def pair_strides(arr: Optional[Sequence[int]]):
     if arr is None:
         return None
