@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 132
+#define SF_VERSION 133
 
 enum {
     SF_OK = 0,
@@ -206,7 +206,9 @@ enum { SF_LAYOUT_K_MAJOR = 0,   /* A[k*lda + m]   /  B[k*ldb + n]   (rows of k) 
        SF_LAYOUT_F16_K_MINOR = 3,  /* B only, split precisions: B points to IEEE fp16 values B[n*ldb + k]
                                     (ldb, strideB in halfs; ldb % 2 == 0); used as they are, no lo part:
                                     a*b = ah*b + al*b.  The stored attention matrix (sf_softmax_rows).   */
-       SF_LAYOUT_F16_KOCT = 5,   /* B only, F16X2 / F16 with a SPLIT_F16 A and M > 96 (the 128-row tile): IEEE fp16 in k-octet
+       SF_LAYOUT_F16_KOCT = 5,   /* B only, F16X2 / F16 with a SPLIT_F16 A.  The tiled kernels take it on the 128-row tile only, i.e. where
+                                    M padded to 128 stays within 1.25 M (103 .. 128, 205 .. 256, 308 .. 384, 410 and up); every other M
+                                    (96 and 192 among them) runs activation-stationary (64 < K <= 640) or is refused: IEEE fp16 in k-octet
                                     planes, element (k, n) at ((k/8)*ldb + n)*8 + k%8 (ldb = pixels per plane, strideB in
                                     halves; 16-byte aligned) -- what a producing sf_gemm stores with c_f16 = 2.  16 bytes =
                                     one MFMA operand octet of one pixel: the consumer moves its B tiles HBM/L2 -> LDS with
@@ -276,14 +278,19 @@ typedef struct SfGemm {
        Only rows < M are written to C16: a last, partial octet keeps its other rows. */
     int32_t c_f16;
     void* C16; int64_t strideC16;
-    /* r_f16 = 2 (split precisions, vector epilogue: the alignment rules of c_f16 = 1 for C): the residual R is not fp32
-       planes but an fp16 k-octet image (SF_LAYOUT_F16_KOCT: element (m, n) at ((m/8)*ldr + n)*8 + m%8, ldr = pixels per
-       plane, strideR in halves, 16-byte aligned, no grouping) -- e.g. the tensor that was this block's GEMM operand, read
-       a second time as the residual without an fp32 copy of it ever having been written (correlation features). */
+    /* r_f16 = 2 (split precisions): the residual R is not fp32 planes but an fp16 k-octet image (SF_LAYOUT_F16_KOCT: element
+       (m, n) at ((m/8)*ldr + n)*8 + m%8, ldr = pixels per plane >= N, strideR in halves and % 8 == 0, 16-byte aligned, no
+       grouping) -- e.g. the tensor that was this block's GEMM operand, read a second time as the residual without an fp32
+       copy of it ever having been written (correlation features).  The tiled kernels take it with SF_EPI_RES_GELU_DW1 and
+       the vector epilogue only (the alignment rules of c_f16 = 1 for C; c_f16 != 2); the activation-stationary kernel with
+       every residual epilogue (RES, RES_GELU, RES_GELU_DW1, AXPY), every output format and no alignment rule for C, at
+       K <= 512. */
     int32_t r_f16;
     /* SPLIT_F16 weights: the k extent the A_hi / A_lo planes are zero-padded to is K rounded up to a multiple of a_k_pad
        (0 or 32: the minimum the tiled kernels need; 128: what the activation-stationary kernel needs -- streamflow_amd
-       packs 128). */
+       packs 128).  Any other multiple of 32 promises at least the minimum and is taken as such; a value that is negative or
+       no multiple of 32 is refused (SF_ERR_BAD_ARG).  Nothing past [K so padded][lda_h] is read, and of the lda_h rows of a
+       plane only the first M padded to 128 (lda_h may be larger, a multiple of 128). */
     int32_t a_k_pad;
     /* kernel family: SF_ALGO_AUTO picks per problem; the other two force one (tests, A/B timing) and fail when it cannot run */
     int32_t algo;
@@ -292,13 +299,51 @@ enum { SF_ALGO_AUTO = 0,
        SF_ALGO_TILED = 1,     /* 128 x 128 / 128 x 256 output tiles, operands staged per k-tile (csrc/gemm_split.hip) */
        SF_ALGO_BSTAT = 2 };   /* activation-stationary: a wave keeps the K values of its 32 pixels in registers and the weights
                                  stream past them through LDS (csrc/gemm_bstat.hip): F16X2 / F16, SPLIT_F16 weights with
-                                 a_k_pad = 128, 64 < K <= 640, B as fp32 planes / fp16 rows / k-octets, C as fp32 planes and / or
-                                 k-octets (c_f16 0, 2, 3) */
+                                 a_k_pad = 128, 64 < K <= 640 (with an fp32 residual K <= 384, with a k-octet one K <= 512), B as
+                                 fp32 planes / fp16 rows / k-octets, C as fp32 planes and / or k-octets (c_f16 0, 2, 3), no
+                                 implicit 3x3.  It loads fp16 rows (SF_LAYOUT_F16_K_MAJOR) half by half: N, ldb and strideB may be
+                                 odd and B needs 2-byte alignment only -- the tiled kernels refuse those (even N / ldb / strideB,
+                                 4-byte aligned B) */
 
 /* floats of scratch that let sf_gemm auto-split a problem of this size (0 if it never would) */
 int64_t sf_gemm_split_ws_floats(int M, int N, int K, int batch);
 
+/* Established for SPLIT_F16 weights by tests/test_gpu_gemm_packed.py (every kernel family, one to three products, against float64;
+ * the case lists and the dispatch rules they cover: tests/gemm_packed_cases.py, held against sf_gemm_route on the CPU):
+ *   placement: ldb > N, ldc > N, ldr > N, gaps between images and between row groups, and bases off the allocation's start hold
+ *       for fp32 planes, fp16 rows and the k-octet forms of B, C (c_f16 = 2), C16 and R (r_f16 = 2) alike.  Only [z][m < M][n < N]
+ *       is written -- c_f16 = 2 also writes the rows up to the end of the last octet (finite values), c_f16 = 3 leaves them alone
+ *       -- and no operand is.  Dense, pitched and (where the format allows less than 16 bytes) unaligned placements of one
+ *       problem give bitwise the same result, vector and scalar epilogue included; five runs are bitwise equal.
+ *   the B-direct kernel takes a k-octet B where ceil(N / 256) * ceil(M / 128) * batch >= 384 and M >= 205 (see SF_LAYOUT_F16_KOCT
+ *       for the M it has a tile for) or M in 103 .. 128 with K <= 192; below that the 128 x 128 DMA tile runs the same problem.
+ *   activation-stationary: any N >= 1 (a wave owns its pixels' whole K: pixels [0, n) of a run at N > n are bitwise the run at
+ *       n), any M <= 1024, odd N / ldb / strideB for fp32 planes and fp16 rows. */
 int sf_gemm(const SfGemm* g, void* stream);
+
+/* Which kernel sf_gemm would launch for this descriptor, without launching anything (no GPU needed, pointers are looked at for
+ * their alignment only).  It runs sf_gemm's own validation and dispatch code -- every launch site reports its identity instead of
+ * launching -- so a refused descriptor gets the same return code and sf_last_error() text as from sf_gemm, and `out` is then
+ * left alone. */
+enum { SF_GEMM_FAMILY_FP32_TILED = 1,   /* csrc/gemm.hip: exact fp32 tiles                                                   */
+       SF_GEMM_FAMILY_SPLIT_TILED = 2,  /* csrc/gemm_split.hip: operands staged through registers; told apart by (a_layout,
+                                           b_layout): fp32 / SPLIT_F16 A x fp32 / fp16-rows / stored-fp16 K-minor B          */
+       SF_GEMM_FAMILY_KOCT_DMA = 3,     /* SPLIT_F16 A x k-octet B, both by LDS-DMA, 128 x 128 tile                          */
+       SF_GEMM_FAMILY_BDIRECT = 4,      /* SPLIT_F16 A x k-octet B, 128 x 256 tile, B straight into registers                */
+       SF_GEMM_FAMILY_BSTAT = 5,        /* csrc/gemm_bstat.hip: activation-stationary, general epilogue                      */
+       SF_GEMM_FAMILY_BSTAT_GELU = 6 }; /* activation-stationary, software-pipelined GELU -> k-octets                        */
+typedef struct SfGemmRoute {
+    int32_t family;               /* SF_GEMM_FAMILY_* */
+    int32_t a_layout, b_layout;   /* of the descriptor */
+    int32_t tile_rows;            /* rows of the workgroup tile: 32 / 64 / 128; 0 for the activation-stationary kernels */
+    int32_t products;             /* MFMA products per element: 1 / 2 / 3 (1 for exact fp32) */
+    int32_t nks, res;             /* activation-stationary: k-steps of 16 the instantiation holds (8 / 16 / 24 / 32 / 40) and its
+                                     residual form (0 none, 1 fp32 planes, 2 k-octets; 0 for the pipelined-GELU kernel) */
+    int32_t msplit, n_main;       /* activation-stationary: row ranges per pixel tile (1 .. 4) and the pixel tiles that run whole */
+    int32_t k_splits;             /* slices when the library splits K on its own through split_ws (the second, epilogue kernel is
+                                     implied), else 0 */
+} SfGemmRoute;
+int sf_gemm_route(const SfGemm* g, SfGemmRoute* out);
 
 /* out[i] = R[i] + gamma[0] * sum_s partial[s*split_stride + i]  for n_img images of rows*P floats each
  * (image strides in floats): the AXPY epilogue of gma.py:102 applied after a split-K attn @ v. */

@@ -45,6 +45,15 @@ class SfGemm(C.Structure):
     ]
 
 
+GEMM_FP32_TILED, GEMM_SPLIT_TILED, GEMM_KOCT_DMA, GEMM_BDIRECT, GEMM_BSTAT, GEMM_BSTAT_GELU = 1, 2, 3, 4, 5, 6
+
+
+class SfGemmRoute(C.Structure):
+    """sf_gemm_route's answer: the kernel sf_gemm would launch (SF_GEMM_FAMILY_* and its template parameters)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "a_layout", "b_layout", "tile_rows", "products", "nks", "res", "msplit",
+                                         "n_main", "k_splits")]
+
+
 class SfFfnPair(C.Structure):
     _fields_ = [
         ("X", _vp), ("strideX", _i64), ("ldx", _i64),
@@ -140,6 +149,7 @@ SIGNATURES = {
     "sf_corr_build_blocked32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "sf_corr_lookup_blocked32": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sf_gemm": (_i, [C.POINTER(SfGemm), _vp]),
+    "sf_gemm_route": (_i, [C.POINTER(SfGemm), C.POINTER(SfGemmRoute)]),
     "sf_gemm_split_ws_floats": (_i64, [_i, _i, _i, _i]),
     "sf_gma_flash_ws_bytes": (_i64, [_i, _i]),
     "sf_gma_flash_pack_qk": (_i, [_vp, _i64, _vp, _i64, _i, _i, _f, _i, _vp]),
@@ -219,7 +229,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 132:
+    if lib.sf_version() < 133:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -256,6 +256,7 @@ int launch_cfg(const SfGemm& g, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     dim3 grid(sf::ceil_div(g.N, BN) * sf::ceil_div(g.M, BM) * g.batch);      // 1-D: see sf::xcd_tile
     const int lay = g.a_layout * 2 + g.b_layout;
+    if (sf::gemm_route_probe()) return sf::gemm_route_report(SF_GEMM_FAMILY_FP32_TILED, BM, 1);
     switch (lay) {
         case 0: hipLaunchKernelGGL((gemm_f32_mfma<WM, WN, TM, TN, BK, 0, 0>), grid, dim3(kThreads), 0, st, g); break;
         case 1: hipLaunchKernelGGL((gemm_f32_mfma<WM, WN, TM, TN, BK, 0, 1>), grid, dim3(kThreads), 0, st, g); break;
@@ -285,6 +286,26 @@ int pick_bm(const SfGemm& g) {
 namespace sf {
 int gemm_split_dispatch(const SfGemm& g, hipStream_t st);   // gemm_split.hip
 int64_t gemm_split_ws_floats(int M, int N, int K, int batch);
+
+SfGemmRoute*& gemm_route_probe() {
+    static thread_local SfGemmRoute* probe = nullptr;
+    return probe;
+}
+}
+
+// The route query IS the ordinary call with the probe set: the same checks in the same order, the same messages, and every
+// launch site answers into `r` instead of launching.
+extern "C" int sf_gemm_route(const SfGemm* gp, SfGemmRoute* out) {
+    SF_REQUIRE(out != nullptr, "sf_gemm_route: null out");
+    SfGemmRoute r{};
+    sf::gemm_route_probe() = &r;
+    const int rc = sf_gemm(gp, nullptr);
+    sf::gemm_route_probe() = nullptr;
+    if (rc != SF_OK) return rc;
+    r.a_layout = gp->a_layout;
+    r.b_layout = gp->b_layout;
+    *out = r;
+    return SF_OK;
 }
 
 extern "C" int64_t sf_gemm_split_ws_floats(int M, int N, int K, int batch) {

@@ -787,11 +787,15 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bstat_gk_kernel(const BsArgs
 template <int PM>
 int launch_gk(const BsArgs& a, dim3 grid, hipStream_t st) {
     const int nks = (a.g.K + 15) / 16;
-    if (nks <= 8) hipLaunchKernelGGL((gemm_bstat_gk_kernel<8, PM>), grid, dim3(kThreads), 0, st, a);
-    else if (nks <= 16) hipLaunchKernelGGL((gemm_bstat_gk_kernel<16, PM>), grid, dim3(kThreads), 0, st, a);
-    else if (nks <= 24) hipLaunchKernelGGL((gemm_bstat_gk_kernel<24, PM>), grid, dim3(kThreads), 0, st, a);
-    else if (nks <= 32) hipLaunchKernelGGL((gemm_bstat_gk_kernel<32, PM>), grid, dim3(kThreads), 0, st, a);   // (K = 486: 31 k-steps)
-    else hipLaunchKernelGGL((gemm_bstat_gk_kernel<40, PM>), grid, dim3(kThreads), 0, st, a);
+    // (sf_gemm_route: every branch answers with its own instantiation instead of launching it)
+    const bool probe = sf::gemm_route_probe() != nullptr;
+    int sel;
+    if (nks <= 8) { sel = 8; if (!probe) hipLaunchKernelGGL((gemm_bstat_gk_kernel<8, PM>), grid, dim3(kThreads), 0, st, a); }
+    else if (nks <= 16) { sel = 16; if (!probe) hipLaunchKernelGGL((gemm_bstat_gk_kernel<16, PM>), grid, dim3(kThreads), 0, st, a); }
+    else if (nks <= 24) { sel = 24; if (!probe) hipLaunchKernelGGL((gemm_bstat_gk_kernel<24, PM>), grid, dim3(kThreads), 0, st, a); }
+    else if (nks <= 32) { sel = 32; if (!probe) hipLaunchKernelGGL((gemm_bstat_gk_kernel<32, PM>), grid, dim3(kThreads), 0, st, a); }   // (K = 486: 31 k-steps)
+    else { sel = 40; if (!probe) hipLaunchKernelGGL((gemm_bstat_gk_kernel<40, PM>), grid, dim3(kThreads), 0, st, a); }
+    if (probe) return sf::gemm_route_report(SF_GEMM_FAMILY_BSTAT_GELU, 0, PM, sel, 0, a.msplit, a.n_main);
     return sf::check_launch("sf_gemm(B-stationary, pipelined GELU)");
 }
 
@@ -800,14 +804,19 @@ int launch_res(const BsArgs& a, dim3 grid, hipStream_t st) {
     const SfGemm& g = a.g;
     const bool needs_r = g.epilogue == SF_EPI_RES || g.epilogue == SF_EPI_RES_GELU || g.epilogue == SF_EPI_RES_GELU_DW1 ||
                          g.epilogue == SF_EPI_AXPY;
-    if (!needs_r) hipLaunchKernelGGL((gemm_bstat_kernel<NKS, PM, 0>), grid, dim3(kThreads), 0, st, a);
+    const bool probe = sf::gemm_route_probe() != nullptr;
+    int res = 0;
+    if (!needs_r) { if (!probe) hipLaunchKernelGGL((gemm_bstat_kernel<NKS, PM, 0>), grid, dim3(kThreads), 0, st, a); }
     else if (g.r_f16 == 2) {
-        if constexpr (NKS <= 32) hipLaunchKernelGGL((gemm_bstat_kernel<NKS, PM, 2>), grid, dim3(kThreads), 0, st, a);
+        res = 2;
+        if constexpr (NKS <= 32) { if (!probe) hipLaunchKernelGGL((gemm_bstat_kernel<NKS, PM, 2>), grid, dim3(kThreads), 0, st, a); }
         else return sf::fail(SF_ERR_UNSUPPORTED, "sf_gemm(B-stationary): a k-octet residual needs K <= 512 (register budget)");
     } else {
-        if constexpr (NKS <= 24) hipLaunchKernelGGL((gemm_bstat_kernel<NKS, PM, 1>), grid, dim3(kThreads), 0, st, a);
+        res = 1;
+        if constexpr (NKS <= 24) { if (!probe) hipLaunchKernelGGL((gemm_bstat_kernel<NKS, PM, 1>), grid, dim3(kThreads), 0, st, a); }
         else return sf::fail(SF_ERR_UNSUPPORTED, "sf_gemm(B-stationary): an fp32 residual needs K <= 384 (register budget)");
     }
+    if (probe) return sf::gemm_route_report(SF_GEMM_FAMILY_BSTAT, 0, PM, NKS, res, a.msplit, a.n_main);
     return sf::check_launch("sf_gemm(B-stationary)");
 }
 

@@ -501,6 +501,7 @@ int launch_cfg(const SplitArgs& a, hipStream_t st) {
     const int lay = g.a_layout * 4 + g.b_layout;
     if (lay == 7) {
         if constexpr (!SB && TM * TN == 4) {             // only the 128x128 tile is built for the stored-fp16 B
+            if (sf::gemm_route_probe()) return sf::gemm_route_report(SF_GEMM_FAMILY_SPLIT_TILED, BM, 2);
             hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 1, 3, 2>), grid, dim3(kThreads), 0, st, a);
             return sf::check_launch("sf_gemm(f16x3)");
         }
@@ -527,6 +528,7 @@ int launch_cfg(const SplitArgs& a, hipStream_t st) {
             const bool bd_m = g.M >= SF_GEMM_BD_MIN_M || (g.M > 96 && g.K <= 192);
             if (SF_GEMM_BDIRECT && bd_m && n_wg2 >= SF_GEMM_BD_MIN_WG && g.k_splits <= 1 && (int64_t)g.ldb * 16 * 2 < ((int64_t)1 << 31)) {
                 dim3 grid2(sf::ceil_div(g.N, 256) * sf::ceil_div(g.M, 128) * g.batch);
+                if (sf::gemm_route_probe()) return sf::gemm_route_report(SF_GEMM_FAMILY_BDIRECT, BM, PM);
 #if SF_GEMM_BD256_MIN_M
                 if (PM == 1 && sf::ceil_div(g.M, 256) * 256 == sf::ceil_div(g.M, 128) * 128 && g.M >= SF_GEMM_BD256_MIN_M) {
                     dim3 grid3(sf::ceil_div(g.N, 256) * sf::ceil_div(g.M, 256) * g.batch);
@@ -537,25 +539,30 @@ int launch_cfg(const SplitArgs& a, hipStream_t st) {
                 hipLaunchKernelGGL((gemm_bdirect_kernel<PM>), grid2, dim3(kBdThreads), 0, st, a);
                 return sf::check_launch("sf_gemm(B-direct)");
             }
+            if (sf::gemm_route_probe()) return sf::gemm_route_report(SF_GEMM_FAMILY_KOCT_DMA, BM, PM);
             hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 2, 5, PM>), grid, dim3(kThreads), 0, st, a);
             return sf::check_launch("sf_gemm(f16x2, k-octet B)");
         }
-        return sf::fail(SF_ERR_UNSUPPORTED, "sf_gemm: SF_LAYOUT_F16_KOCT B needs the 128-row tile (M > 96) and F16X2 / F16");
+        return sf::fail(SF_ERR_UNSUPPORTED, "sf_gemm: SF_LAYOUT_F16_KOCT B needs the 128-row tile (M padded to 128 within 1.25 M: 103 .. 128, 205 .. 256, 308 .. 384, "
+                                            "410 and up) and F16X2 / F16; SF_ALGO_AUTO runs other M activation-stationary where 64 < K <= 640");
     }
     if (lay == 12) {                                     // split weights x stored-fp16 K-major activations (F16X2 only)
         if constexpr (!SB) {
+            if (sf::gemm_route_probe()) return sf::gemm_route_report(SF_GEMM_FAMILY_SPLIT_TILED, BM, PM);
             hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 2, 4, PM>), grid, dim3(kThreads), 0, st, a);
             return sf::check_launch("sf_gemm(f16x2, fp16 B)");
         }
         return sf::fail(SF_ERR_UNSUPPORTED, "sf_gemm: SF_LAYOUT_F16_K_MAJOR B needs SF_PRECISION_F16X2");
     }
+    const bool probe = sf::gemm_route_probe() != nullptr;   // (sf_gemm_route: the cases below answer instead of launching)
     switch (lay) {
-        case 0: hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 0, 0, PM>), grid, dim3(kThreads), 0, st, a); break;
-        case 5: hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 1, 1, PM>), grid, dim3(kThreads), 0, st, a); break;
-        case 8: hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 2, 0, PM>), grid, dim3(kThreads), 0, st, a); break;
+        case 0: if (!probe) hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 0, 0, PM>), grid, dim3(kThreads), 0, st, a); break;
+        case 5: if (!probe) hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 1, 1, PM>), grid, dim3(kThreads), 0, st, a); break;
+        case 8: if (!probe) hipLaunchKernelGGL((gemm_f16x3_mfma<WM, WN, TM, TN, 2, 0, PM>), grid, dim3(kThreads), 0, st, a); break;
         default: return sf::fail(SF_ERR_UNSUPPORTED, "sf_gemm(f16x3): layout combination a=%d b=%d not built",
                                  g.a_layout, g.b_layout);
     }
+    if (probe) return sf::gemm_route_report(SF_GEMM_FAMILY_SPLIT_TILED, BM, PM);
     return sf::check_launch("sf_gemm(f16x3)");
 }
 
@@ -720,6 +727,7 @@ int gemm_split_dispatch(const SfGemm& g, hipStream_t st) {
             p.k_splits = ks; p.split_stride = slab;
             const int rc = gemm_split_dispatch_inner(p, st);
             if (rc != SF_OK) return rc;
+            if (SfGemmRoute* probe = gemm_route_probe()) { probe->k_splits = ks; return SF_OK; }
             return launch_splitk_epilogue(g, g.split_ws, ks, slab, st);
         }
     }
@@ -741,6 +749,10 @@ int gemm_split_dispatch_inner(const SfGemm& g, hipStream_t st) {
         if (!g.A_hi || !g.A_lo || g.lda_h < (g.M + 127) / 128 * 128 || (g.lda_h & 127) ||
             ((reinterpret_cast<uintptr_t>(g.A_hi) | reinterpret_cast<uintptr_t>(g.A_lo)) & 15))
             return fail(SF_ERR_BAD_ARG, "sf_gemm(f16x3): SPLIT_F16 A needs 16-byte aligned A_hi/A_lo and lda_h = M padded to 128");
+        // the kernels read the planes up to K rounded up to 32 (the activation-stationary one to 128, gemm_bstat_ok): a smaller or
+        // odd padding promise would let them read past what the caller packed
+        if (g.a_k_pad < 0 || (g.a_k_pad & 31))
+            return fail(SF_ERR_BAD_ARG, "sf_gemm(f16x3): a_k_pad must be 0 or a multiple of 32 (the k extent A_hi/A_lo are zero-padded to)");
         a.a_bytes = (int64_t)((g.K + 31) / 32 * 32) * g.lda_h * 2;          // [K up to 32 / 8][lda_h rows][8] halfs
     } else {
         a.a_bytes = span_bytes(g.a_layout, g.M, g.K, g.lda, 0, 0);

@@ -13,6 +13,17 @@ namespace sf {
 char* err_buf();
 int fail(int code, const char* fmt, ...);
 
+// sf_gemm_route: while this thread-local pointer is set (by sf_gemm_route, around the ordinary sf_gemm call) every launch site of
+// the GEMM dispatch reports which kernel it is there and returns SF_OK instead of launching.  One copy of the rules: the probe sits
+// where the launches are.  (defined in gemm.hip)
+SfGemmRoute*& gemm_route_probe();
+inline int gemm_route_report(int family, int tile_rows, int products, int nks = 0, int res = 0, int msplit = 0, int n_main = 0) {
+    SfGemmRoute& r = *gemm_route_probe();
+    r.family = family; r.tile_rows = tile_rows; r.products = products;
+    r.nks = nks; r.res = res; r.msplit = msplit; r.n_main = n_main;
+    return SF_OK;
+}
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SF_ERR_HIP, "%s: %s", what, hipGetErrorString(e));

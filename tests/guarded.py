@@ -60,6 +60,50 @@ class Guarded:
                                 b.view(torch.int32) if b.dtype == torch.float32 else b.view(torch.int16)))
 
 
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int16)
+
+
+class Placed(Guarded):
+    """A Guarded view at an EXPLICIT placement (tests/gemm_packed_cases.py place(): off, ld, stride, group_stride in elements), for
+    the k-octet forms in particular: a base 16 bytes into the allocation, ld > cols, a gap of a multiple of 8 halves after every
+    image, groups of rows with a gap between them.  kind: 'f32' fp32 planes, 'h16' fp16 rows, 'koct' fp16 k-octet planes.
+    k-octet views whose rows are no multiple of 8 have a TAIL: the rows past `rows` in the last octet.  They are outside the view,
+    but a consumer may read them (they meet zero weights and must be finite) and a c_f16 = 2 producer may write them: `tail_fill`
+    puts a finite value there, tail() returns them and outside_unchanged(tail_free=True) leaves them out of the comparison."""
+
+    def __init__(self, dev, kind, batch, rows, cols, off, ld, stride, group, group_stride, fill, tail_fill=None):
+        koct = kind == "koct"
+        super().__init__(dev, batch, rows, cols, off, ld, stride, fill, torch.float32 if kind == "f32" else torch.float16,
+                         group=group, group_stride=group_stride, koct=koct, tail=8)
+        self.kind = kind
+        self.tail_idx = None
+        if koct and rows % 8:
+            rl = (rows - 1) % group if group else rows - 1                  # last row, counted inside its group
+            goff = ((rows - 1) // group) * group_stride if group else 0
+            z = np.arange(batch)[:, None, None]
+            r = np.arange(rl % 8 + 1, 8)[None, :, None]
+            c = np.arange(cols)[None, None, :]
+            self.tail_idx = torch.from_numpy((off + z * stride + goff + ((rl // 8) * ld + c) * 8 + r).reshape(-1)).to(dev)
+            if tail_fill is not None:
+                self.buf[self.tail_idx] = tail_fill
+        self.snap = self.buf.clone()
+
+    def tail(self):
+        return self.buf[self.tail_idx].float()
+
+    def outside_unchanged(self, before=None, tail_free=False):
+        ref = self.snap if before is None else before
+        keep = ~self.inside
+        if tail_free and self.tail_idx is not None:
+            keep[self.tail_idx] = False
+        return bool(torch.equal(_bits(self.buf[keep]), _bits(ref[keep])))
+
+    def untouched(self):
+        """The whole allocation, view included, is bitwise what put() left (operands)."""
+        return bool(torch.equal(_bits(self.buf), _bits(self.snap)))
+
+
 class GuardedBytes:
     """A byte workspace of exactly `size` bytes between two guard bands of `guard` bytes (a multiple of `align`, so the workspace keeps
     the allocation's alignment; shift > 0 moves it off that alignment).  The workspace is filled with `fill`, the bands with `band`;

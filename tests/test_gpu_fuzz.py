@@ -642,10 +642,15 @@ def test_attention_cores_koct_handover(dev, seed):
 @pytest.mark.parametrize("single", [False, True])
 @pytest.mark.parametrize("epi", ["none", "gelu_koct", "res_gelu_dw1"])
 def test_koct_gemm_dispatch_branches_vs_float64(dev, M, K, single, epi):
-    """Every dispatch branch of the k-octet-fed GEMM (csrc/gemm_split.hip, lay == 13): the 128 x 128 DMA kernel (M <= 128 with
-    a long K), the B-direct kernel as 1 x 8 waves (single-product layers, and 192 <= M < 512) and 2 x 4 waves (two-product,
-    M >= 512), the short-K one-row-tile rule -- with split and single-product weights and the three epilogue families of the
-    update block, ragged pixel counts and two images, against a float64 product of the SAME fp16-rounded operands."""
+    """The k-octet-fed GEMM under SF_ALGO_AUTO at the update block's layer shapes, with split and single-product weights and the
+    three epilogue families of the update block, ragged pixel counts and two images, against a float64 product of the SAME
+    fp16-rounded operands.  What it reaches: the 128 x 128 DMA tile (fp32 planes out at M = 126, 128, 256, 384, 640, 960, and
+    k-octets out where K > 640), the activation-stationary kernels (k-octets out at 64 < K <= 640: the pipelined-GELU form; every
+    output at M = 200 and 486, whose padding to 128 rows wastes more than a quarter) and the tiled family's refusal of M = 200.
+    It does NOT reach the B-direct 128 x 256 kernel: at 2 images of 1012 pixels the largest shape gives
+    ceil(N / 256) * ceil(M / 128) * batch = 64 workgroups, and launch_cfg asks for SF_GEMM_BD_MIN_WG = 384 (the threshold is
+    younger than this test).  B-direct against float64: tests/test_gpu_gemm_packed.py (parts B and C), with the route of every
+    run confirmed by sf_gemm_route."""
     from streamflow_amd import ops
     from streamflow_amd.ops import Planes, PackedLinear
     g = torch.Generator().manual_seed(M * 7 + K + int(single))
