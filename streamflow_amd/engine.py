@@ -292,16 +292,66 @@ class HotPathWeights:
 ATTN_ROW_LIMIT = 1 << 28          # floats per image the GEMM epilogue can address with 32-bit offsets (1 GiB)
 
 
-class _Plan:
-    """Buffers for one (clips, pairs, h, w) shape."""
+@dataclass(frozen=True)
+class GmaPlan:
+    """How one plan runs the global motion aggregation (gma.py:53-65,91-104); chosen by resolve_gma, nowhere else.  form: 'matrix' =
+    attention matrix materialised once per clip, 'chunked' = its row chunks recomputed every iteration; the fused kernel's softmax weights
+    'recompute'd every iteration, 'stored' once per clip and streamed, or 'hybrid' = stored for n_store images, recomputed for the rest."""
+    form: str
+    attn_rows: int     # rows of the matrix kept per image: P, or one chunk; 1 in the fused forms (no matrix)
+    attn_f16: bool     # the matrix is kept in fp16 (half the bytes of the HBM-bound attn @ v; 4e-6 px mean EPE)
+    k_splits: int      # split-K of attn @ v over the materialised matrix
+    n_store: int       # images whose softmax weights are stored
+    project_v: bool    # to_v + the v pack of the fused kernel as one launch (sf_gma_flash_project_v)
+    auto_stored: bool  # 'stored' chosen by gma_mode='flash' itself (options.stored_auto_px)
+    fused = property(lambda self: self.form in ("recompute", "stored", "hybrid"))
 
-    def __init__(self, W: HotPathWeights, Bc: int, h: int, w: int, D: int, device, attn_chunk_rows: int = 0,
-                 attn_f16: bool = False, corr_f16: bool = False, flash: Optional[bool] = None, shadows: bool = False,
-                 corr_blocked: bool = False, koct_io: bool = False, stored_p: bool = False, stored_p_max_bytes: int = 0,
-                 stored_frac: float = 1.0, corr_blocked32: bool = False):
+
+def resolve_gma(gma_mode: str, precision: int, flash_qk_products: int, options: EngineOptions, n_img: int, P: int,
+                project_ok: bool) -> GmaPlan:
+    """The GMA form of a plan over n_img images of P pixels.  project_ok: the fused v projection can run (fp16 activations, k-octet
+    copies active for this grid, to_v 128 x 128 without bias).  Host arithmetic and the library's sizing functions only.
+    (The stored weights' limit of 4 GiB per image, a rule of attn.hip, belongs here once the library exports it.)"""
+    split = precision != ops.PRECISION_FP32
+    fused = gma_mode in ("flash", "stored", "hybrid")
+    if fused and not split:
+        raise RuntimeError(f"gma_mode={gma_mode!r} needs a split precision (f16x3 / f16x2); the exact fp32 mode keeps "
+                           "the materialised / chunked attention path")
+    # materialise the N x N matrix once (core/gma.py) when an image's matrix fits the kernels' 32-bit offsets; otherwise (1080p: N = 32400
+    # -> 4.2 GB per image) recompute it in row chunks every iteration, as the reference's demo does through flash-attn (demo.py:235-258)
+    chunk = int(options.attn_chunk_rows)
+    lim = max(1, (ATTN_ROW_LIMIT - 1) // P)
+    rows = P if (chunk <= 0 and P * P < ATTN_ROW_LIMIT) else min(P, lim if chunk <= 0 else min(chunk, lim))
+    ks = max(1, min(4, int(options.attn_k_splits))) if (split and P % 4 == 0) else 1
+    if not (fused or (gma_mode == "auto" and split and rows < P and chunk <= 0)):    # ('auto': fused when the matrix would be chunked)
+        return GmaPlan("matrix" if rows == P else "chunked", rows, split and P % 2 == 0, ks, 0, False, False)
+    # high-resolution grids keep the fused kernel's softmax weights for the loop, and so do split-precision logits at every grid
+    # (same results; the measurements are at EngineOptions.stored_auto_px)
+    auto_stored = (gma_mode == "flash" and int(options.stored_auto_px) > 0 and
+                   (P >= int(options.stored_auto_px) or flash_qk_products >= 2) and
+                   ops.gma_stored_p_bytes(n_img, P) <= (int(options.stored_auto_max_gb) << 30))
+    whole = gma_mode == "stored" or auto_stored
+    # 'hybrid': stored weights (HBM-bound) and recompute (power-bound) side by side on disjoint images (DESIGN.md section 12).  Both
+    # halves read the projected v, and neither may be small enough for the key-split form -- else the recompute kernel runs alone
+    n_store = n_img if whole else max(0, min(n_img, int(round(n_img * float(options.hybrid_store_pct) / 100.0))))
+    project_v = bool(options.project_v and project_ok)
+    halves_ok = lambda: project_v and ops.gma_no_key_split(n_store, P) and ops.gma_no_key_split(n_img - n_store, P)
+    if not ((whole or gma_mode == "hybrid") and options.flash_stats and n_store > 0 and (n_store == n_img or halves_ok()) and
+            ops.gma_stored_p_bytes(n_store, P) <= (int(options.stored_p_max_gb) << 30)):
+        n_store = 0
+    form = "recompute" if n_store == 0 else ("stored" if n_store == n_img else "hybrid")
+    return GmaPlan(form, 1, False, ks, n_store, project_v, bool(auto_stored and n_store > 0))
+
+
+class _Plan:
+    """Buffers for one (clips, pairs, h, w) shape; of the GMA buffers only those that the form `gma` reads."""
+
+    def __init__(self, W: HotPathWeights, Bc: int, h: int, w: int, D: int, device, gma: GmaPlan, corr_f16: bool = False,
+                 shadows: bool = False, corr_blocked: bool = False, koct_io: bool = False, corr_blocked32: bool = False):
         Pn = W.pairs
         n, P = Bc * Pn, h * w
         self.Bc, self.Pn, self.h, self.w, self.n, self.P, self.D = Bc, Pn, h, w, n, P, D
+        self.gma, self.flash, self.attn_rows, self.n_store, self.auto_stored = gma, gma.fused, gma.attn_rows, gma.n_store, gma.auto_stored
         if (h >> 3) < 1 or (w >> 3) < 1:
             raise RuntimeError(f"feature grid {h}x{w} too small for a 4-level pyramid (need >= 8x8)")
         if (h >> 3) < 2 or (w >> 3) < 2:
@@ -334,40 +384,12 @@ class _Plan:
                          for s in self.lvl_pair_stride]
             # scratch of the split-precision volume build: (hi, lo) fp16 planes of every f1 / f2 image
             self.corr_ws = torch.empty(max(ops.corr_build_ws_bytes(Bc, Pn, D, h, w), 16), dtype=torch.uint8, device=device)
-        # GMA attention: materialise the N x N matrix once (reference core/gma.py) when an image's matrix fits the
-        # kernels' 32-bit offsets; otherwise (high resolution, e.g. 1080p: N = 32400 -> 4.2 GB per image) recompute
-        # softmax(q k^T) v in row chunks every iteration, which is what the reference's demo does through
-        # flash-attn (demo.py:235-258): same mathematics, no N^2 tensor kept.
-        if attn_chunk_rows <= 0 and P * P < ATTN_ROW_LIMIT:
-            self.attn_rows = P
-        else:
-            lim = max(1, (ATTN_ROW_LIMIT - 1) // P)
-            self.attn_rows = min(P, lim if attn_chunk_rows <= 0 else min(attn_chunk_rows, lim))
-        # fused path (sf_gma_flash_*): softmax(q k^T) v recomputed inside one kernel per iteration, logits never leave
-        # the CU.  flash=None: used whenever the matrix would have to be chunked (split precisions only).
-        self.flash = bool(flash) if flash is not None else (attn_f16 and self.attn_rows < P and attn_chunk_rows <= 0)
-        self.flash_ws = None
-        self.pbuf = None
-        self.n_store = 0
-        if self.flash:
-            self.flash_ws = torch.empty(ops.gma_flash_ws_bytes(n, P), dtype=torch.uint8, device=device)
-            self.attn_rows = 1                     # no attention matrix at all: placeholders only
-            # 'stored': the softmax weights kept for the loop in the fragment order of the second contraction (sf_gma_flash_store_p)
-            # ('hybrid': for the first n_store images only -- the stream of stored weights is HBM-bound, the recompute kernel is
-            # bound by the chip's power budget: run side by side on disjoint images they use different resources, section 12)
-            self.n_store = n if stored_frac >= 1.0 else max(0, min(n, int(round(n * stored_frac))))
-            if self.n_store < n and not (self.n_store > 0 and ops.gma_no_key_split(self.n_store, P) and ops.gma_no_key_split(n - self.n_store, P)):
-                self.n_store = 0                   # (a launch small enough for the key-split form keeps the recompute kernel alone)
-            if stored_p and self.n_store > 0 and ops.gma_stored_p_bytes(self.n_store, P) <= stored_p_max_bytes:
-                self.pbuf = torch.empty(ops.gma_stored_p_bytes(self.n_store, P), dtype=torch.uint8, device=device)
-            else:
-                self.n_store = 0
-        self.attn = torch.empty(n, self.attn_rows, P, dtype=torch.float32, device=device)
-        # split-precision modes keep the materialised matrix in fp16 (half the bytes of the HBM-bound attn @ v that
-        # every iteration repeats; measured effect on the final flow: 4e-6 px mean EPE); self.attn is then only the
-        # logits scratch of the one-time softmax
-        self.attn16 = (torch.empty(n, self.attn_rows, P, dtype=torch.float16, device=device)
-                       if attn_f16 and P % 2 == 0 else None)       # whole matrix, or one row chunk (high resolution)
+        self.flash_ws = torch.empty(ops.gma_flash_ws_bytes(n, P), dtype=torch.uint8, device=device) if gma.fused else None
+        # the softmax weights kept for the loop in the fragment order of the second contraction (sf_gma_flash_store_p)
+        self.pbuf = torch.empty(ops.gma_stored_p_bytes(gma.n_store, P), dtype=torch.uint8, device=device) if gma.n_store else None
+        # the matrix, or one row chunk of it; with the fp16 copy self.attn is only the logits scratch of the softmax
+        self.attn = None if gma.fused else torch.empty(n, gma.attn_rows, P, dtype=torch.float32, device=device)
+        self.attn16 = torch.empty(n, gma.attn_rows, P, dtype=torch.float16, device=device) if gma.attn_f16 else None
         spec = [("qk", 2 * HDIM), ("corr", COR_PLANES), ("flow", 2), ("hid", 960), ("xa", 640), ("xb", 640),
                 ("cor256", 256), ("cat256", 256), ("f128", 128),
                 ("concat", 640),                       # [nets | inps | mf | mf_global | mf_temporal]
@@ -375,8 +397,10 @@ class _Plan:
                 ("delta", 2),                          # == [Bc][2*Pn][P]
                 ("m256", 256), ("mask", 576), ("coords1", 2),
                 ("hid2", 192), ("xa2", 128), ("xb2", 128),       # scratch of the flow branch (runs concurrently)
-                ("part", 128 * 4),                               # split-K slabs of attn @ v: [4][n][128][P]
+                ("part", HDIM * gma.k_splits),                   # split-K slabs of attn @ v: [k_splits][n][128][P]
                 ("splitws", 1024)]                                # scratch for sf_gemm's automatic split-K
+        if gma.form != "matrix" or gma.k_splits == 1:
+            spec = [(nm, r) for nm, r in spec if nm != "part"]
         if self.corr_blocked:
             spec = [(nm, r) for nm, r in spec if nm != "corr"]          # no fp32 planes of the correlation features at all
         # tensors of the motion encoder that are ONLY input / output of SK blocks (cor = convc1's output, cat(cor, flo), convf1's
@@ -468,13 +492,7 @@ class HotPathEngine:
         # global aggregation) are enqueued on a second stream, so the tails of one chain's small kernels are
         # filled by the other; inside a captured graph these become parallel branches.
         self.parallel_branches = self.options.parallel_branches
-        self.auto_split_k = self.options.auto_split_k
-        self.attn_chunk_rows = int(self.options.attn_chunk_rows)            # > 0 forces the recompute path
-        self.attn_k_splits = min(4, int(self.options.attn_k_splits))        # 1 = no split-K (<= 4)
-        # GMA aggregation: 'matrix' = attention matrix materialised once (gma.py), chunked recompute when it cannot be
-        # kept; 'flash' = fused recompute kernel every iteration (demo.py:235-258); 'auto' = flash exactly when the
-        # matrix would have to be chunked (high resolution)
-        self.gma_mode = gma_mode or "auto"
+        self.gma_mode = gma_mode or "auto"                                  # (what a plan runs for it: resolve_gma)
         if self.gma_mode not in ("auto", "matrix", "flash", "stored", "hybrid"):
             raise RuntimeError(f"gma_mode must be auto, matrix, flash, stored or hybrid, got {self.gma_mode!r}")
         # MFMA products per logit of the fused kernel: 3 = split precision (fp32-class), 2 / 1 = k / q and k in fp16
@@ -487,10 +505,6 @@ class HotPathEngine:
             self._probe_stream = torch.cuda.Stream(device=self.device)
             self.clock_counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         self._chain_streams = [torch.cuda.Stream(device=self.device) for _ in range(3)]
-        # Where the main stream has no concurrent branch (corr encoder, motion-encoder tail, GRU + flow head) a batch of an
-        # even number of clips is cut in two halves that run as two chains on two streams: a dependent kernel boundary costs
-        # ~8 us on this part and each chain hides the other's.  options.split_solo = 0 / 2 / 4 chains.
-        self.split_solo = int(self.options.split_solo)
         self.W = HotPathWeights(state_dict, self.device, T)
         # layers whose weights are used as ONE fp16 value in the f16x2 mode (see presets.py: chosen by measured EPE)
         self.single_layers = tuple(single_layers or ())
@@ -521,32 +535,17 @@ class HotPathEngine:
         """Buffers (and captured graph) for one input shape; at most `max_plans` shapes are kept, least recently used
         evicted first (a dataset with varying image sizes would otherwise pin several GB per distinct shape)."""
         key = (Bc, h, w, D)
+        f16_act = self.precision in (ops.PRECISION_F16X2, ops.PRECISION_F16)
+        shadows = bool(self.options.shadows and (h * w) % 4 == 0 and f16_act and self.options.hidden_f16)
+        gma = resolve_gma(self.gma_mode, self.precision, self.flash_qk_products, self.options, Bc * self.W.pairs, h * w,
+                          project_ok=shadows and self.W.to_v.M == self.W.to_v.K == HDIM and self.W.to_v.bias is None)
         pl = self._plans.pop(key, None)
-        if pl is None:
+        if pl is None or pl.gma != gma:                              # (a mode or precision assigned after the plan was made)
             while len(self._plans) >= max(1, self.max_plans):
                 self._plans.pop(next(iter(self._plans)))            # dicts keep insertion order: first = oldest
-            split = self.precision != ops.PRECISION_FP32
-            if self.gma_mode in ("flash", "stored", "hybrid") and not split:
-                raise RuntimeError(f"gma_mode={self.gma_mode!r} needs a split precision (f16x3 / f16x2); the exact fp32 mode keeps "
-                                   "the materialised / chunked attention path")
-            flash = {"auto": None, "matrix": False, "flash": True, "stored": True, "hybrid": True}[self.gma_mode]
-            # high-resolution grids: the fused path keeps its softmax weights for the loop (options.stored_auto_px; same results)
-            n_img = Bc * self.W.pairs
-            # ... and so do split-precision logits at every grid (two / three MFMA products per logit make the recompute 2.5x the stream:
-            # 1483 vs 608 us per iteration at the Sintel grid, fp32_class 168 -> 182 ff/s)
-            auto_stored = (self.gma_mode == "flash" and int(self.options.stored_auto_px) > 0 and
-                           (h * w >= int(self.options.stored_auto_px) or self.flash_qk_products >= 2)
-                           and ops.gma_stored_p_bytes(n_img, h * w) <= (int(self.options.stored_auto_max_gb) << 30))
-            pl = _Plan(self.W, Bc, h, w, D, self.device, self.attn_chunk_rows, attn_f16=split, corr_f16=self.corr_f16,
-                       flash=flash, shadows=(self.options.shadows and (h * w) % 4 == 0 and
-                                             self.precision in (ops.PRECISION_F16X2, ops.PRECISION_F16) and
-                                             self.options.hidden_f16),
+            pl = _Plan(self.W, Bc, h, w, D, self.device, gma, corr_f16=self.corr_f16, shadows=shadows,
                        corr_blocked=self.corr_blocked, corr_blocked32=self.corr_blocked32,
-                       koct_io=self.options.koct_io and self.options.hidden_koct,   # (k-octet-only blocks need k-octet producers)
-                       stored_p=((self.gma_mode in ("stored", "hybrid") or auto_stored) and self.options.flash_stats),
-                       stored_frac=(1.0 if (self.gma_mode == "stored" or auto_stored) else float(self.options.hybrid_store_pct) / 100.0),
-                       stored_p_max_bytes=int(self.options.stored_p_max_gb) << 30)
-            pl.auto_stored = bool(auto_stored and pl.pbuf is not None)
+                       koct_io=self.options.koct_io and self.options.hidden_koct)   # (k-octet-only blocks need k-octet producers)
         self._plans[key] = pl                                        # (re)insert as most recent
         return pl
 
@@ -555,7 +554,7 @@ class HotPathEngine:
         """The launch context of one forward over plan `pl`: passed to every op (no process-wide launch state)."""
         o = self.options
         return ops.Ctx(precision=self.precision,
-                       split_ws=pl.splitws.tensor().view(-1) if self.auto_split_k else None,
+                       split_ws=pl.splitws.tensor().view(-1) if o.auto_split_k else None,
                        shadows=o.shadows, shadow_fused=o.shadow_fused, flash_stats=o.flash_stats,
                        hidden_f16=o.hidden_f16, hidden_koct=o.hidden_koct, pw_fold=o.pw_fold, x2_f16=o.x2_f16,
                        ffn_pairs=o.ffn_pairs, head_pairs=o.head_pairs, sk_tail=o.sk_tail, sk_tail_all=o.sk_tail_all)
@@ -582,6 +581,64 @@ class HotPathEngine:
             for img in range(n):
                 ops.softmax_rows(pl.attn[img], rows, P, out16=None if pl.attn16 is None else pl.attn16[img])
 
+    def _aggregate_matrix(self, cx: ops.Ctx, pl: _Plan) -> None:
+        """mfg = mf + gamma * attn @ v over the materialised matrix ('matrix'), or chunk by chunk over its recomputed rows ('chunked')."""
+        W, g, P, n = self.W, pl.gma, pl.P, pl.n
+        attn_ptr, attn_lay = (pl.attn16.data_ptr(), LAYOUT_F16_K_MINOR) if pl.attn16 is not None else (pl.attn.data_ptr(), LAYOUT_K_MINOR)
+        if g.form == "matrix" and g.k_splits > 1:
+            # attn @ v streams the N x N matrix (HBM-bound) but has only N/128 * images workgroups: split K so that
+            # enough bytes are in flight; partial products go to slabs, combined with the AXPY of gma.py:102
+            ops.gemm_raw(cx, A=pl.v128.ptr, B=attn_ptr, C=pl.part.ptr, M=HDIM, N=P, K=P, batch=n, lda=P, ldb=P,
+                         ldc=P, strideA=pl.v128.img_stride, strideB=P * P, strideC=HDIM * P,       # slabs: [split][img][128][P]
+                         a_layout=LAYOUT_K_MINOR, b_layout=attn_lay, alpha=1.0, epilogue=EPI_NONE,
+                         k_splits=g.k_splits, split_stride=n * HDIM * P)
+            ops.splitk_combine(pl.part.base[pl.part.off:], n * HDIM * P, g.k_splits, HDIM * P, pl.mf, W.gamma, pl.mfg)
+            return
+        for i0 in range(0, P, g.attn_rows):         # ('matrix': the one chunk of all P rows, made by _setup)
+            rows = min(g.attn_rows, P - i0)
+            if g.form == "chunked":                 # high-resolution path: the attention rows again every iteration (K6' of SURVEY.md)
+                self._attention_rows(cx, pl, i0, rows)
+            ops.gemm_raw(cx, A=pl.v128.ptr, B=attn_ptr, C=pl.mfg.ptr + 4 * i0, R=pl.mf.ptr + 4 * i0, gamma=W.gamma.data_ptr(),
+                         M=HDIM, N=rows, K=P, batch=n, lda=P, ldb=P, ldc=P, ldr=P, strideA=pl.v128.img_stride,
+                         strideB=g.attn_rows * P, strideC=pl.mfg.img_stride, strideR=pl.mf.img_stride,
+                         a_layout=LAYOUT_K_MINOR, b_layout=attn_lay, alpha=1.0, epilogue=EPI_AXPY)
+
+    def _gma(self, cx: ops.Ctx, pl: _Plan, concurrent: bool, launch_recompute: bool) -> None:
+        """Global aggregation  mfg = mf + gamma * attn @ to_v(mf)  (gma.py:91-104) in the plan's form, on the current stream.
+        concurrent: another branch runs beside it; launch_recompute = False leaves the recompute kernel to the caller's chains."""
+        W, g, n, P = self.W, pl.gma, pl.n, pl.P
+        if not g.fused:
+            ops.gemm(W.to_v, pl.mf, pl.v128, EPI_NONE, cx=cx)
+            self._aggregate_matrix(cx, pl)
+            ops.refresh_shadow(pl.mfg, cx)                          # (the fused kernels write the k-octet copy themselves)
+            return
+        if g.project_v:                 # fp16 activations: to_v and the v pack are ONE launch from mf's k-octet copy
+            ops.gma_flash_project_v(pl.flash_ws, W.to_v, pl.mf, cx=cx)
+            v128 = None
+        else:
+            # v has ONE reader, the pack of the fused kernel (which rounds it to fp16): fp16 rows where the fp16 hand-over is active
+            v128 = _scratch(pl.v128, n, HDIM, f16=True) if (hidden_f16_ok(cx, P) and cx.x2_f16) else pl.v128
+            ops.gemm(W.to_v, pl.mf, v128, EPI_NONE, cx=cx)
+        if g.form == "stored":
+            # the stored weights streamed past v (gma.py:99-102): half the matrix-core work of the recompute, HBM-bound
+            ops.gma_stored_aggregate(pl.flash_ws, pl.pbuf, v128, pl.mf, W.gamma, pl.mfg, cx=cx)
+        elif g.form == "hybrid":
+            # images [0, n_store) through the stored weights on a chain stream (HBM-bound), the rest through the recompute kernel
+            # on this one (power-bound): two launches that want different resources, side by side; both read the projected v
+            ns, main = g.n_store, torch.cuda.current_stream()
+            sc = self._chain_streams[0] if concurrent else main     # (never compared by identity: current_stream() makes a new object)
+            if concurrent:
+                sc.wait_stream(main)
+            with torch.cuda.stream(sc):
+                ops.gma_stored_aggregate(self._flash_ws_sub(pl, 0, ns), pl.pbuf, None, _sub(pl.mf, 0, ns), W.gamma, _sub(pl.mfg, 0, ns),
+                                         cx=cx.no_split() if concurrent else cx)
+            ops.gma_flash_aggregate(self._flash_ws_sub(pl, ns, n - ns), None, _sub(pl.mf, ns, n - ns), W.gamma, _sub(pl.mfg, ns, n - ns),
+                                    self.flash_qk_products, use_stats=True, cx=cx)
+            if concurrent:
+                main.wait_stream(sc)
+        elif launch_recompute:          # fused recompute (K6' of SURVEY.md): one kernel, online softmax, logits never written
+            ops.gma_flash_aggregate(pl.flash_ws, v128, pl.mf, W.gamma, pl.mfg, self.flash_qk_products, use_stats=True, cx=cx)
+
     # ---------------------------------------------------------------------------------------------
     def _setup(self, cx: ops.Ctx, pl: _Plan, fmaps: torch.Tensor, cnets: torch.Tensor) -> None:
         """Everything before the iteration loop: volumes, context split, GMA attention matrix."""
@@ -602,12 +659,12 @@ class HotPathEngine:
             ops.refresh_shadow(pl.inps, cs)
             # a6: attn = softmax(scale * q k^T) over the context features (gma.py:53-65), computed once
             ops.gemm(W.to_qk, pl.inps, pl.qk, EPI_NONE, cx=cs)
-            if pl.flash:
+            if pl.gma.fused:
                 # q, k are constant over the loop: packed once, and the softmax statistics of every query with them
                 ops.gma_flash_pack_qk(pl.qk, pl.flash_ws, float(HDIM) ** -0.5, stats_qk_products=self.flash_qk_products, cx=cs)
-                if pl.pbuf is not None:             # ... and the softmax weights themselves (gma.py:53-65: `attn`), kept for the loop
+                if pl.gma.form != "recompute":      # ... and the softmax weights themselves (gma.py:53-65: `attn`), kept for the loop
                     ops.gma_flash_store_p(self._flash_ws_sub(pl, 0, pl.n_store), pl.pbuf, pl.n_store, P, self.flash_qk_products, cx=cs)
-            elif pl.attn_rows == P:
+            elif pl.gma.form == "matrix":
                 self._attention_rows(cs, pl, 0, P)
         # a1+a2: all pairs, one launch.  pair t = (frame t, frame t+1)
         if pl.corr_blocked or pl.corr_blocked32:
@@ -653,8 +710,9 @@ class HotPathEngine:
             ops.refresh_shadow(pl.corr, cx)
         else:
             ops.corr_lookup(pl.lvls, pl.lvl_pair_stride, pl.coords1, pl.corr, Bc, Pn, h, w, cx=cx, pitch=pl.corr_pitch)
-        # image ranges of the chains: whole clips when the clip count divides, else (a single clip, an odd batch) one chain
-        nch = self.split_solo if (self.split_solo in (2, 4) and side is not main) else 1
+        # sections without a concurrent branch run as half-batch chains (options.split_solo; each hides the other's ~8 us kernel
+        # boundaries).  Image ranges: whole clips when the clip count divides, else (one clip, an odd batch) one chain
+        nch = self.options.split_solo if (self.options.split_solo in (2, 4) and side is not main) else 1
         parts = [(c * (n // nch), n // nch) for c in range(nch)] if (nch > 1 and Bc % nch == 0) else [(0, n)]
         split = len(parts) > 1
 
@@ -704,69 +762,11 @@ class HotPathEngine:
                 h256 = _handover(cs, pl.h256, pl.n, 256, P, consumer_rows=HDIM)        # fc1 -> fc2 only
                 ops.gemm(W.fc1, ln, h256, EPI_GELU, cx=cs)
                 ops.gemm(W.fc2, h256, pl.mft, EPI_RES, R=pl.tx128, cx=cs)
-        # a7: global aggregation  mfg = mf + gamma * attn @ to_v(mf)   (gma.py:91-104), main stream
-        # v has ONE reader, the pack of the fused kernel (which rounds it to fp16): fp16 rows where the fp16 hand-over is active
-        v128 = _scratch(pl.v128, pl.n, HDIM, f16=True) if (pl.flash and hidden_f16_ok(cx, P) and cx.x2_f16) else pl.v128
-        # fused recompute path with fp16 activations: to_v and the v pack are ONE launch from mf's k-octet copy (options.project_v)
-        project = pl.flash and self.options.project_v and ops.gma_flash_project_ok(W.to_v, pl.mf, cx)
-        # options.gma_per_chain: one fused launch per half-batch chain (each a workspace sub-range without the key-split form)
-        gma_in_chains = bool(self.options.gma_per_chain and pl.flash and pl.pbuf is None and project and split and
+        # a7: global aggregation (main stream).  options.gma_per_chain: the recompute kernel as one launch per half-batch chain (each
+        # a workspace sub-range without the key-split form), in front of each chain's GRU below
+        gma_in_chains = bool(self.options.gma_per_chain and pl.gma.form == "recompute" and pl.gma.project_v and split and
                              all(ops.gma_no_key_split(cnt, P) for _, cnt in parts))
-        if project:
-            ops.gma_flash_project_v(pl.flash_ws, W.to_v, pl.mf, cx=cx)
-            v128 = None
-        else:
-            ops.gemm(W.to_v, pl.mf, v128, EPI_NONE, cx=cx)
-        ks = self.attn_k_splits if self.precision != ops.PRECISION_FP32 else 1
-        attn_ptr, attn_lay = ((pl.attn16.data_ptr(), LAYOUT_F16_K_MINOR) if pl.attn16 is not None
-                              else (pl.attn.data_ptr(), LAYOUT_K_MINOR))
-        if pl.flash and pl.pbuf is not None and pl.n_store == n:
-            # the stored weights streamed past v (gma.py:99-102): half the matrix-core work of the recompute, HBM-bound
-            ops.gma_stored_aggregate(pl.flash_ws, pl.pbuf, v128, pl.mf, W.gamma, pl.mfg, cx=cx)
-        elif pl.flash and pl.pbuf is not None:
-            # hybrid: images [0, n_store) through the stored weights on a chain stream (HBM-bound), the rest through the recompute
-            # kernel on the main stream (power-bound): two launches that want different resources, side by side
-            ns = pl.n_store
-            assert project and v128 is None, "hybrid GMA needs the fused v projection (fp16-activation presets)"
-            sc = self._chain_streams[0] if side is not main else main
-            if sc is not main:
-                sc.wait_stream(main)
-            with torch.cuda.stream(sc):
-                ops.gma_stored_aggregate(self._flash_ws_sub(pl, 0, ns), pl.pbuf, None, _sub(pl.mf, 0, ns), W.gamma, _sub(pl.mfg, 0, ns), cx=cs)
-            ops.gma_flash_aggregate(self._flash_ws_sub(pl, ns, n - ns), None, _sub(pl.mf, ns, n - ns), W.gamma, _sub(pl.mfg, ns, n - ns),
-                                    self.flash_qk_products, use_stats=True, cx=cx)
-            if sc is not main:
-                main.wait_stream(sc)
-        elif pl.flash and gma_in_chains:
-            pass                                                    # launched per chain below, in front of each chain's GRU
-        elif pl.flash:
-            # fused recompute (K6' of SURVEY.md): one kernel, online softmax, logits never written
-            ops.gma_flash_aggregate(pl.flash_ws, v128, pl.mf, W.gamma, pl.mfg, self.flash_qk_products, use_stats=True, cx=cx)
-        elif pl.attn_rows < P:
-            # high-resolution path: recompute the attention rows chunk by chunk (K6' of SURVEY.md)
-            for i0 in range(0, P, pl.attn_rows):
-                rows = min(pl.attn_rows, P - i0)
-                self._attention_rows(cx, pl, i0, rows)
-                ops.gemm_raw(cx, A=pl.v128.ptr, B=attn_ptr, C=pl.mfg.ptr + 4 * i0, R=pl.mf.ptr + 4 * i0,
-                             gamma=W.gamma.data_ptr(), M=HDIM, N=rows, K=P, batch=n, lda=P, ldb=P, ldc=P, ldr=P,
-                             strideA=pl.v128.img_stride, strideB=pl.attn_rows * P, strideC=pl.mfg.img_stride,
-                             strideR=pl.mf.img_stride, a_layout=LAYOUT_K_MINOR, b_layout=attn_lay, alpha=1.0,
-                             epilogue=EPI_AXPY)
-        elif ks > 1 and P % 4 == 0:
-            # attn @ v streams the N x N matrix (HBM-bound) but has only N/128 * images workgroups: split K so that
-            # enough bytes are in flight; partial products go to slabs, combined with the AXPY of gma.py:102
-            ops.gemm_raw(cx, A=pl.v128.ptr, B=attn_ptr, C=pl.part.ptr, M=HDIM, N=P, K=P, batch=n, lda=P, ldb=P,
-                         ldc=P, strideA=pl.v128.img_stride, strideB=P * P, strideC=HDIM * P,       # slabs: [split][img][128][P]
-                         a_layout=LAYOUT_K_MINOR, b_layout=attn_lay, alpha=1.0, epilogue=EPI_NONE,
-                         k_splits=ks, split_stride=n * HDIM * P)
-            ops.splitk_combine(pl.part.base[pl.part.off:], n * HDIM * P, ks, HDIM * P, pl.mf, W.gamma, pl.mfg)
-        else:
-            ops.gemm_raw(cx, A=pl.v128.ptr, B=attn_ptr, C=pl.mfg.ptr, R=pl.mf.ptr, gamma=W.gamma.data_ptr(),
-                         M=HDIM, N=P, K=P, batch=n, lda=P, ldb=P, ldc=P, ldr=P, strideA=pl.v128.img_stride,
-                         strideB=P * P, strideC=pl.mfg.img_stride, strideR=pl.mf.img_stride,
-                         a_layout=LAYOUT_K_MINOR, b_layout=attn_lay, alpha=1.0, epilogue=EPI_AXPY)
-        if not pl.flash:
-            ops.refresh_shadow(pl.mfg, cx)                          # (the flash kernel writes the k-octet copy itself)
+        self._gma(cx, pl, side is not main, launch_recompute=not gma_in_chains)
         if not gma_in_chains:
             join()
         # "gru": SKBlock(640 -> 128) over cat[nets, inps, mf, mfg, mft]; new nets overwrite the nets slice
@@ -881,10 +881,9 @@ class HotPathEngine:
             pl.cnets_in = torch.empty_like(cnets)
         pl.fmaps_in.copy_(fmaps)
         pl.cnets_in.copy_(cnets)
-        # (the schedule reads these MUTABLE attributes -- bench.py / tests assign eng.parallel_branches etc. after construction:
-        # the values in force at capture time are part of the key)
+        # (callers assign eng.parallel_branches after construction: the value in force at capture time is part of the key)
         key = key + (self.precision, self.options, self.gma_mode, self.flash_qk_products, self.corr_f16, self.single_layers,
-                     self.parallel_branches, self.split_solo, self.auto_split_k, self.attn_chunk_rows, self.attn_k_splits)
+                     self.parallel_branches)
         if pl.graph is None or pl.graph_key != key:
             # warm-up outside capture, then capture the whole clip as one graph.  The loop state (coords1, flow)
             # is re-initialised by the caller before every replay, so the graph itself is stateless.

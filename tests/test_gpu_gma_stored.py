@@ -193,3 +193,56 @@ def test_split_precision_logits_keep_their_weights_by_default(dev):
         eng.forward(fm, cn, iters=2)
         pl = next(iter(eng._plans.values()))
         assert (pl.pbuf is not None) == stored and pl.auto_stored == stored
+
+
+@pytest.mark.parametrize("preset, B, h, w", [("fp32_class", 2, 16, 24),       # f16x3: no fp16 activations, so no fused v projection
+                                             ("config2_fp16", 1, 17, 21)])    # P % 4 != 0: no k-octet copies at this grid
+def test_engine_hybrid_mode_without_the_v_projection_recomputes(dev, preset, B, h, w):
+    """gma_mode='hybrid' needs v projected into the fused workspace, which both halves read.  Where that launch is not available the plan
+    resolves to the recompute form (engine.resolve_gma) instead of failing inside the loop: no weights stored, and the flows of
+    gma_mode='flash' without stored weights (stored_auto_px = 0), bit for bit, eager and graph replay."""
+    from streamflow_amd import presets, synthetic as syn
+    from streamflow_amd.engine import EngineOptions, HotPathEngine
+    T = 3
+    params = syn.make_params(5, T)
+    fm, cn = (t.to(dev) for t in syn.make_features(85, B, T, h, w))
+    outs, plans = {}, []
+    for mode in ("hybrid", "flash"):               # (hybrid first: this is where the loop's assert used to fire)
+        kw = dict(presets.engine_kwargs(preset), gma_mode=mode, options=EngineOptions(stored_auto_px=0))
+        for graph in (False, True):
+            eng = HotPathEngine(params, device=dev, T=T, use_graph=graph, **kw)
+            eng.forward(fm, cn, iters=2)
+            outs[(mode, graph)] = [f.clone() for f in eng.forward(fm, cn, iters=2)[0]]
+            plans.append(next(iter(eng._plans.values())))
+            assert plans[-1].n_store == 0 and plans[-1].pbuf is None
+    for key, val in outs.items():
+        for a, b in zip(val, outs[("flash", False)]):
+            assert torch.equal(a, b), key
+    assert all(pl.gma.form == "recompute" and not pl.gma.project_v for pl in plans)
+
+
+@pytest.mark.parametrize("parallel", [True, False])
+def test_hybrid_launches_keep_their_streams(dev, monkeypatch, parallel):
+    """Where the hybrid halves are enqueued: with parallel branches the stored half on a chain stream of its own beside the recompute
+    half on the main stream; with parallel_branches = False (serial launches, e.g. for per-kernel timing) every call of the forward
+    on ONE stream.  The C-ABI calls of one eager forward, each with the stream it was enqueued on."""
+    from streamflow_amd import _lib, presets, synthetic as syn
+    from streamflow_amd.engine import HotPathEngine
+    T, B, h, w = 3, 2, 16, 24                          # 4 images of 384 pixels: two halves of 2, neither with the key-split form
+    fm, cn = (t.to(dev) for t in syn.make_features(86, B, T, h, w))
+    eng = HotPathEngine(syn.make_params(5, T), device=dev, T=T, **dict(presets.engine_kwargs("config2_fp16"), gma_mode="hybrid"))
+    eng.parallel_branches = parallel                   # (assigned after construction, as bench.py --serial-branches does)
+    calls, check = [], _lib.check
+    monkeypatch.setattr(_lib, "check", lambda status, what="": (calls.append((what, torch.cuda.current_stream().cuda_stream)),
+                                                                check(status, what))[1])
+    eng.forward(fm, cn, iters=2)
+    torch.cuda.synchronize()
+    assert next(iter(eng._plans.values())).gma.form == "hybrid"
+    on = lambda name: {s for what, s in calls if what == name}
+    main = on("sf_gma_flash_project_v")
+    assert len(main) == 1 and on("sf_gma_flash_aggregate") == main and len(on("sf_gma_stored_aggregate")) == 1
+    if parallel:
+        assert on("sf_gma_stored_aggregate").isdisjoint(main | on("sf_temporal_block"))       # not the main, not the side stream
+        assert len({s for _, s in calls}) == 3                                                # main, side, one chain stream
+    else:
+        assert {s for _, s in calls} == main
