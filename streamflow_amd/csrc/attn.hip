@@ -25,10 +25,6 @@
 #include "sf_common.h"
 #include <cstdlib>
 
-#ifndef SF_FLASH_XCD_MAP
-#define SF_FLASH_XCD_MAP 1
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -181,26 +177,22 @@ __device__ __forceinline__ float xor32(float v) {          // value of lane ^ 32
     return __shfl_xor(v, 32, 64);
 }
 
-#ifndef SF_FLASH_PRIO
-#define SF_FLASH_PRIO 0   // 1: s_setprio(1) around the two MFMA clusters of a tile (A/B knob, tools/build_variant.sh)
-#endif
-#ifndef SF_FLASH_V1
-#define SF_FLASH_V1 1     // one-product kernel: ONE V stage (48 KB of LDS, 3 workgroups per CU) instead of two (64 KB, 2 per CU)
-#endif
+// (s_setprio(1) around the two MFMA clusters of a tile measured nothing: 712-726 vs 716-721 us, docs/DESIGN_log_r5.md 12.7)
 // MODE 0: self-contained online softmax (running maximum, rescale, row sum).  MODE 1: the statistics of the workspace are
 // used (accumulators start at -max, weights are exp2 of the accumulator, the result is scaled by the stored 1 / row sum).
 // MODE 2: the statistics pass -- logits and the online maximum / sum only (no V tile, no P V), writes (max, 1 / sum).
 // MODE 3: the store pass -- MODE 1's softmax weights (exp2 of the logit minus the stored maximum, rounded to fp16: bit for bit what
 // MODE 1 multiplies) written to g.pbuf as the B fragments of the second contraction, no V tile, no P V (gma_pv_kernel below).
 template <int QKP, int MODE>
-__global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1 && SF_FLASH_V1) ? 3 : 2)) void gma_flash_kernel(const FlashArgs g) {
+__global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1) ? 3 : 2)) void gma_flash_kernel(const FlashArgs g) {
     constexpr bool kKlo = (QKP == 3);
     constexpr bool kUseStats = MODE == 1 || MODE == 3, kStatsPass = MODE == 2, kStoreP = MODE == 3;
     constexpr bool kNoPV = kStatsPass || kStoreP;
     constexpr int KSTAGE = KPLANE * (kKlo ? 2 : 1);
-    // kV1: K tiles double-buffered, V single-buffered.  V(t) is requested at the top of tile t (every wave has finished
+    // kV1 (the one-product kernel): K tiles double-buffered, ONE V stage -- 48 KB of LDS, 3 workgroups per CU instead of 64 KB and 2
+    // (765 -> 730 us per iteration at the Sintel grid, docs/DESIGN_log_r1_r3.md).  V(t) is requested at the top of tile t (every wave has finished
     // P V of tile t-1 by then) and has the logits + softmax of tile t to land; a second barrier precedes P V.
-    constexpr bool kV1 = (QKP == 1) && SF_FLASH_V1;
+    constexpr bool kV1 = (QKP == 1);
     constexpr int NV = kV1 ? 1 : 2;
     __shared__ __attribute__((aligned(1024))) char smem[2 * KSTAGE + NV * VTILE];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -208,13 +200,9 @@ __global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1 && SF_FLASH_V1) ? 
     const int khalf = lane >> 5, l31 = lane & 31;
     // (query tile, image) from the linear workgroup id such that every XCD walks whole images: the K / V planes of an image (3.6 MB at
     // the Sintel grid) are read by all its query tiles and live in ONE XCD's L2 instead of eight (round 5; FETCH_SIZE of the kernel
-    // 889 -> see profiles: the requests went to the Infinity Cache before)
-#if SF_FLASH_XCD_MAP
+    // 889 -> see profiles: the requests went to the Infinity Cache before; profiles/r05_flash_xcd_ab.txt: 598.4 -> 596.7 us, +0.4 % on the step)
     const int wg_lin = sf::xcd_linear_id((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
     const int img = wg_lin / (int)gridDim.x, q0 = (wg_lin % (int)gridDim.x) * BQ;
-#else
-    const int img = blockIdx.y, q0 = blockIdx.x * BQ;
-#endif
     const int P = g.P, Ppad = g.Ppad;
     const int plane = (int)plane_bytes(Ppad);                       // < 2 GiB (host-checked)
     const char* ws = g.ws + (int64_t)img * img_ws_bytes(Ppad);
@@ -299,9 +287,6 @@ __global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1 && SF_FLASH_V1) ? 
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[sub][r] = kUseStats ? -st_m : 0.f;     // (a lane holds ONE query: its -max is the start value)
         }
-#if SF_FLASH_PRIO
-        __builtin_amdgcn_s_setprio(1);                            // (experiment: MFMA clusters at raised priority, guide T5)
-#endif
 #pragma unroll
         for (int ks = 0; ks < HD / 16; ++ks) {
 #pragma unroll
@@ -316,9 +301,6 @@ __global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1 && SF_FLASH_V1) ? 
                 s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], s[sub], 0, 0, 0);
             }
         }
-#if SF_FLASH_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         // ---- online softmax for this lane's query ----
         if ((t + 1) * BJ > P) {                                   // last tile with padded keys (workgroup-uniform)
 #pragma unroll
@@ -387,9 +369,6 @@ __global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1 && SF_FLASH_V1) ? 
             __builtin_amdgcn_s_barrier();
         }
         // ---- O^T += V^T P^T ----
-#if SF_FLASH_PRIO
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
@@ -398,9 +377,6 @@ __global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1 && SF_FLASH_V1) ? 
                 o[td] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[kk], o[td], 0, 0, 0);
             }
         }
-#if SF_FLASH_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
     }
 
     // ---- epilogue: out[d][q] = mf[d][q] + gamma * O^T[d][q] / rowsum ----
@@ -456,9 +432,6 @@ __global__ __launch_bounds__(256, (QKP == 3) ? 1 : ((QKP == 1 && SF_FLASH_V1) ? 
 // exp2, one conversion), then P V of tile t.  K and V tiles both double-buffered, requested a whole iteration before their use,
 // ONE barrier per key tile.  Two workgroups per CU (64 KB of LDS, <= 256 registers).  Statistics mode only (accumulators start at
 // -max): the logits, the fp16 weights and the MFMA order of P V are those of gma_flash_kernel<QKP, 1> -- bit-identical results.
-#ifndef SF_FLASH_PIPE
-#define SF_FLASH_PIPE 1
-#endif
 template <int QKP>
 __global__ __launch_bounds__(256, (QKP == 1) ? 2 : 1) void gma_flash_pipe_kernel(const FlashArgs g) {
     constexpr bool kKlo = (QKP == 3);
@@ -468,12 +441,8 @@ __global__ __launch_bounds__(256, (QKP == 1) ? 2 : 1) void gma_flash_pipe_kernel
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, l31 = lane & 31;
-#if SF_FLASH_XCD_MAP
     const int wg_lin = sf::xcd_linear_id((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
     const int img = wg_lin / (int)gridDim.x, q0 = (wg_lin % (int)gridDim.x) * BQ;
-#else
-    const int img = blockIdx.y, q0 = blockIdx.x * BQ;
-#endif
     const int P = g.P, Ppad = g.Ppad;
     const int plane = (int)plane_bytes(Ppad);
     const char* ws = g.ws + (int64_t)img * img_ws_bytes(Ppad);
@@ -698,21 +667,14 @@ __global__ __launch_bounds__(256, (QKP == 1) ? 2 : 1) void gma_flash_pipe_kernel
 #ifndef SF_PV_NT
 #define SF_PV_NT 2              // cache policy of the weight stream's loads (2 = non-temporal): A/B knob, tools/gma_stored_bench.py
 #endif
-#ifndef SF_PV_ABLATE
-#define SF_PV_ABLATE 0          // timing ablations: 1 = no V tiles requested, 2 = no weight loads, 3 = no MFMAs
-#endif
 __global__ __launch_bounds__(256, SF_PV_WAVES) void gma_pv_kernel(const FlashArgs g) {
     constexpr int PD = 4, NVB = 3;                                 // P tiles in registers, V tiles in LDS
     __shared__ __attribute__((aligned(1024))) char smem[NVB * VTILE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, l31 = lane & 31;
-#if SF_FLASH_XCD_MAP
     const int wg_lin = sf::xcd_linear_id((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
     const int img = wg_lin / (int)gridDim.x, q0 = (wg_lin % (int)gridDim.x) * BQ;
-#else
-    const int img = blockIdx.y, q0 = blockIdx.x * BQ;
-#endif
     const int P = g.P, Ppad = g.Ppad;
     const int plane = (int)plane_bytes(Ppad);
     const char* ws = g.ws + (int64_t)img * img_ws_bytes(Ppad);
@@ -733,7 +695,7 @@ __global__ __launch_bounds__(256, SF_PV_WAVES) void gma_pv_kernel(const FlashArg
         for (int i = 0; i < 4; ++i) {
             const int piece = wave * 4 + i;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr)(smem + buf * VTILE + piece * 1024), 16,
-                                                     (SF_PV_ABLATE == 1) ? (int)0x7ffffff0 : lane * 16 + t * (BJ * HD * 2) + piece * 1024, 0, 0, 0);
+                                                     lane * 16 + t * (BJ * HD * 2) + piece * 1024, 0, 0, 0);
         }
     };
     f16x8 pf[PD][4];
@@ -741,7 +703,7 @@ __global__ __launch_bounds__(256, SF_PV_WAVES) void gma_pv_kernel(const FlashArg
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk)
             dst[kk] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                rp, (SF_PV_ABLATE == 2) ? (int)0xfffffff0u : (int)(p_lane + (unsigned)t * p_tile + kk * 1024), 0, SF_PV_NT));
+                rp, (int)(p_lane + (unsigned)t * p_tile + kk * 1024), 0, SF_PV_NT));
     };
     f32x16 o[HD / 32];
 #pragma unroll
@@ -775,11 +737,7 @@ __global__ __launch_bounds__(256, SF_PV_WAVES) void gma_pv_kernel(const FlashArg
 #pragma unroll
                     for (int td = 0; td < HD / 32; ++td) {
                         const f16x8 vf = *reinterpret_cast<const f16x8*>(vb + ((2 * kk + khalf) * HD + td * 32 + l31) * 16);
-#if SF_PV_ABLATE == 3
-                        o[td][kk] += (float)vf[0] * (float)pf[u % PD][kk][0];
-#else
                         o[td] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[u % PD][kk], o[td], 0, 0, 0);
-#endif
                     }
                 }
                 // issue order, pinned: the V fragment reads run kAhead MFMAs ahead of their use (left alone hipcc reads two fragments,
@@ -918,7 +876,7 @@ static int flash_aggregate(void* ws, int64_t ws_bytes, const void* v_, int v_f16
     // measured (profiles/r06_flash_pipe_ab.txt): with ONE product per logit the pipelined form is 2-3 % SLOWER than the round-5 kernel
     // (621 vs 605 us inside the step: the kernel sits at the chip's power budget, overlapping the units inside a wave buys nothing),
     // with three products it is 4 % faster (1481 vs 1549 us): used for the split-precision logits only.  SF_FLASH_PIPE=2 forces it.
-    const bool pipe = SF_FLASH_PIPE && !(pe && atoi(pe) == 0) && (qk_products >= 2 || (pe && atoi(pe) == 2));
+    const bool pipe = !(pe && atoi(pe) == 0) && (qk_products >= 2 || (pe && atoi(pe) == 2));
     if (use_stats && pipe) {                                  // the software-pipelined form of the statistics mode (same results)
         switch (qk_products) {
             case 1: hipLaunchKernelGGL((gma_flash_pipe_kernel<1>), grid, dim3(256), 0, (hipStream_t)stream, g); break;

@@ -15,7 +15,6 @@
 // kernel is bound by VALU issue, 47 TFLOP/s of fp32 FMA.)
 #include "sf_common.h"
 #include <climits>
-#include <cstdlib>
 #include "split_operand.h"
 
 namespace {
@@ -165,19 +164,10 @@ struct DwmArgs {
     int stride16;     // LDS row stride in 16-byte units (= 8 halfs)
     int vec_ok;       // rows are 16-byte aligned: float4 staging loads
     int plane_bytes;  // bytes of one staged LDS plane (kIn = 2: rounded up to whole 4-KB DMA pieces)
-#ifdef SF_DW_TIMERS
-    long long* ts;    // SF_DW_TS_BUF: per-workgroup phase cycles (tools/dwconv_one.py)
-#endif
 };
 
-#ifndef SF_DW_FOLD_SINGLE
-#define SF_DW_FOLD_SINGLE 0
-#endif
-#ifndef SF_DW_FOLD
-#define SF_DW_FOLD 1
-#endif
 #ifndef SF_DW_TG
-#define SF_DW_TG 4      // phase timers (tools/dwconv_one.py, -DSF_DW_TIMERS): with 2 tiles per wave the tile loop ran at 5.9k
+#define SF_DW_TG 4      // phase timers (docs/DESIGN_log_r1_r3.md): with 2 tiles per wave the tile loop ran at 5.9k
                         // cycles per pair against 1.4k of MFMA issue -- every kernel row waited for its ds_read_b128 round
                         // trip behind 6 MFMAs; 4 tiles put 12 MFMAs behind each round trip
 #endif
@@ -189,9 +179,6 @@ struct DwmArgs {
 // of three and two; both planes are still staged, the residual stays exact.  kProd = 1 (SF_PRECISION_F16, a single-product
 // layer of the mixed preset): the WEIGHTS are one round-to-nearest fp16 too -- one MFMA per kernel row and tile, half the
 // Toeplitz registers (60), three workgroups per CU.
-#ifndef SF_GEMM_FAST_GELU
-#define SF_GEMM_FAST_GELU 1
-#endif
 #ifndef SF_DW_MINWG
 #define SF_DW_MINWG 2
 #endif
@@ -211,8 +198,9 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
     // w'[centre] = w[centre] + 1 -- exact to the split's 2^-22 with hi + lo weights (kProd = 2).  It removes the epilogue's per-output
     // 2-byte LDS reads of x: 16 per tile group against 60 (15 x 15) / 28 (7 x 7) fragment reads, in a kernel that is LDS-bound, and
     // they were the ones with bank conflicts (SQ_LDS_BANK_CONFLICT 9 % / 17 % of the LDS cycles: rows 4 apart are 288 dwords apart).
-    // Single-product layers (kProd = 1) would round w + 1 to fp16 (2^-12 |x| on the residual): SF_DW_FOLD_SINGLE, off.
-    constexpr bool kFoldRes = SF_DW_FOLD && (kIn == 2) && (kProd == 2 || (kProd == 1 && SF_DW_FOLD_SINGLE));
+    // Single-product layers (kProd = 1) would round w + 1 to fp16 (2^-12 |x| on the residual): not folded.
+    // (profiles/r05_dw_fold_ab.txt: folded 378.4 ff/s, not folded 375.1; folded in single-product layers too: hard-case EPE 5.7e-4 -> 6.5e-4)
+    constexpr bool kFoldRes = (kIn == 2) && (kProd == 2);
     typedef __attribute__((address_space(3))) void* lds_ptr;
     constexpr int R = KS / 2;
     constexpr int WZ = 64;                                      // zero-padded weight row: w[ky][j - 24]
@@ -278,10 +266,6 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
         bl[ky] = s8.lo;                                          // (dead for kProd = 1)
     }
     const float bv = g.bias[c];
-#ifdef SF_DW_TIMERS
-    long long t_stage = 0, t_comp = 0;
-    const long long t_begin = __builtin_readcyclecounter();
-#endif
     const int ntx = g.w16 / 16, nty = g.strip_h / 16;
     const int ngroups = nty * ((ntx + TG - 1) / TG);            // groups of up to TG adjacent column tiles
 
@@ -295,9 +279,6 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
         void* yp = kOutF16 ? (void*)(reinterpret_cast<_Float16*>(g.y) + img * g.y_img_stride + (int64_t)c * g.h * g.w)
                            : (void*)(g.y + img * g.y_img_stride + (int64_t)c * g.h * g.w);
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(yp, 0, g.h * g.w * (kOutF16 ? 2 : 4), 0x00020000);
-#ifdef SF_DW_TIMERS
-        const long long t0 = __builtin_readcyclecounter();
-#endif
         if constexpr (kIn == 2) {
             // this wave's pieces of the strip have landed: they are older than the 16 output stores of its last tile group of
             // the previous image, which stay in flight (vmcnt retires in order); a wave without a group has no stores
@@ -325,11 +306,7 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
                 const bool live = idx < rows_in * noct;
                 const bool rowok = live && gy >= 0 && gy < g.h;
                 off[u] = live ? (ry_ * g.stride16 + co) * 16 : -1;
-#if defined(SF_DW_ABLATE) && SF_DW_ABLATE == 2
-                if (false) {
-#else
                 if (kIn == 0 && rowok && g.vec_ok && gx >= 0 && gx + 8 <= g.w) {
-#endif
                     const float4 q0 = *reinterpret_cast<const float4*>(xp + gy * g.w + gx);
                     const float4 q1 = *reinterpret_cast<const float4*>(xp + gy * g.w + gx + 4);
                     v[u][0] = q0.x; v[u][1] = q0.y; v[u][2] = q0.z; v[u][3] = q0.w;
@@ -337,11 +314,7 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
                 } else {
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
-#if defined(SF_DW_ABLATE) && SF_DW_ABLATE == 2
-                        v[u][i] = (float)(idx + i) * 1e-4f;
-#else
                         v[u][i] = (rowok && gx + i >= 0 && gx + i < g.w) ? (kIn == 0 ? xp[gy * g.w + gx + i] : (float)xh[gy * g.w + gx + i]) : 0.f;
-#endif
                 }
             }
 #pragma unroll
@@ -355,10 +328,6 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         }
-#ifdef SF_DW_TIMERS
-        const long long t1 = __builtin_readcyclecounter();
-        t_stage += t1 - t0;
-#endif
 
         for (int grp = wave; grp < ngroups; grp += 4) {
             const int ty = grp % nty, tx0 = (grp / nty) * TG;
@@ -384,13 +353,8 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
                 ah[0][j] = *reinterpret_cast<const f16x8*>(hb + offj[j]);
                 if constexpr (kProd == 3) al[0][j] = *reinterpret_cast<const f16x8*>(lo + offj[j]);
             }
-#if defined(SF_DW_ABLATE) && SF_DW_ABLATE == 3
-#pragma unroll
-            for (int ky = 0; ky < 1; ++ky) {
-#else
 #pragma unroll
             for (int ky = 0; ky < KS; ++ky) {
-#endif
                 const int cur = ky & 1, nxt = cur ^ 1;
                 if (ky + 1 < KS) {
 #pragma unroll
@@ -430,14 +394,10 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
                             t[u] = xv + (acc[j][r + u] + bv);
                         }
                     }
-                    const sf::f32x2 a = sf::gelu2<(kProd <= 2) && kOutF16 && SF_GEMM_FAST_GELU>(t);   // polynomial GELU where the result leaves as fp16
+                    const sf::f32x2 a = sf::gelu2<(kProd <= 2) && kOutF16>(t);   // polynomial GELU where the result leaves as fp16
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
-#if defined(SF_DW_ABLATE) && SF_DW_ABLATE == 1
-                        const bool ok = a[u] == 123.456f;              // (never true: the value still has to be computed)
-#else
                         const bool ok = (gx0 + j * 16 < g.w) && (gy0 + r + u < g.h);
-#endif
                         const int so = ok ? off0 + ((r + u) * g.w + j * 16) * EB : (int)0x80000000u;
                         if constexpr (kOutF16) {
                             const _Float16 o = (_Float16)a[u];
@@ -449,16 +409,7 @@ __global__ __launch_bounds__(256, kProd == 1 ? 3 : ((KS == 15 && kProd == 2) ? S
                     }
                 }
         }
-#ifdef SF_DW_TIMERS
-        t_comp += __builtin_readcyclecounter() - t1;
-#endif
     }
-#ifdef SF_DW_TIMERS
-    if (g.ts && tid == 0) {
-        long long* d = g.ts + ((int64_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4;
-        d[0] = __builtin_readcyclecounter() - t_begin; d[1] = t_stage; d[2] = t_comp; d[3] = img_end - img0;
-    }
-#endif
 }
 
 }  // namespace
@@ -515,9 +466,6 @@ static int dwconv_dispatch(const void* x_, int x_f16, int64_t x_img_stride, cons
         if (groups > n_img) groups = n_img;
         if (groups < 1) groups = 1;
         m.imgs_per_wg = sf::ceil_div(n_img, groups);
-#ifdef SF_DW_TIMERS
-        m.ts = getenv("SF_DW_TS_BUF") ? (long long*)strtoull(getenv("SF_DW_TS_BUF"), nullptr, 0) : nullptr;
-#endif
         dim3 grid(C, strips, sf::ceil_div(n_img, m.imgs_per_wg));
         SF_REQUIRE(strips <= 65535 && grid.z <= 65535, "sf_dwconv_res_gelu: grid too large");
         if (x_f16) {

@@ -16,7 +16,6 @@
 // run inside one of the 324 channel planes (NCHW output, no transposing copy as in the reference).
 #include "sf_common.h"
 #include "split_operand.h"
-#include <cstdlib>
 
 namespace {
 
@@ -45,10 +44,6 @@ struct BuildArgs {
     // DMA kernels: 1-D grid, XCD-aware order [image][patch block][m-tile][patch in block]: the `pblk` target patches of
     // a block stay in the XCD's L2 while all m-tiles stream past them (np = patches per image, mt = m-tiles)
     int np, mt, pblk;
-    int vec_store;               // w % 4 == 0 and 16-byte aligned level bases: transposed 16-byte epilogue stores
-#ifdef SF_CORR_TIMERS
-    long long* ts;               // SF_CORR_TS_BUF: per-workgroup phase timestamps (tools/corr_one.py)
-#endif
 };
 
 struct TileId { int img, m_tile, patch; };
@@ -132,17 +127,14 @@ __device__ __forceinline__ void pyramid_store(const BuildArgs& g, f32x16 (&acc)[
 #ifndef SF_CORR_NT
 #define SF_CORR_NT 2
 #endif
-#ifndef SF_CORR_PACK
-#define SF_CORR_PACK 1      // fp16 level-0 cells leave as packed pairs (A/B knob)
-#endif
     constexpr int kNt = SF_CORR_NT;
     // Store-instruction diet (the epilogue is bound by store ISSUE, not bytes: 240 instructions per wave in the plain
     // form).  (a) After the DPP pooling the 2 / 4 / 4 lanes of a pooling group hold the SAME level-1 / 2 / 3 value, so
     // lane k of a group stores source row ri + k: one instruction covers 2 / 4 / 4 source rows (112 -> 44).  (b) fp16
     // cells, even width: lanes 2j and 2j+1 exchange one value over DPP so that the even lane owns columns (2j, 2j+1) of
     // source row ri and the odd lane the same two columns of row ri + 1: one 4-byte store per lane and register PAIR
-    // (128 -> 64), same 64-byte runs.  Values and roundings are unchanged.
-    const bool pack0 = (ES == 2) && (g.wl[0] & 1) == 0 && SF_CORR_PACK;
+    // (128 -> 64), same 64-byte runs.  Values and roundings are unchanged (fp16 build 1.69 -> 1.57 ms: docs/DESIGN_log_r1_r3.md).
+    const bool pack0 = (ES == 2) && (g.wl[0] & 1) == 0;
     const int odd = l31 & 1;
     const int vo0p = (!kGuard || x < g.wl[0]) ? ((4 * khalf + odd) * P0 + (l31 & ~1)) * ES : kDrop;
     const int k1 = l31 & 1, k2 = l31 & 3, k3 = l31 & 7;       // which source row of a group this lane stores (levels 1..3)
@@ -239,146 +231,18 @@ __device__ __forceinline__ void pyramid_store(const BuildArgs& g, f32x16 (&acc)[
     }
 }
 
-// ---- vector store side (w % 4 == 0): 16-byte stores after a transpose through LDS -------------------------------------
-// The dword path above issues 170 store instructions per wave (256 bytes each) and the build is bound by exactly that:
-// store ISSUE, not bandwidth (2.8 TB/s of writes at best).  Here every pair of patch rows (two 32x32 accumulator
-// tiles) goes through a per-wave LDS scratch (row stride 36 floats: conflict-free dword writes, 16-byte aligned rows)
-// and comes back with a lane owning FOUR consecutive target columns of one source row (row = lane/8 + 8q, columns
-// 4*(lane%8)..+3): level 0 leaves as 16-byte (fp32) / 8-byte (fp16) stores, 1 KB per instruction, and the horizontal
-// pooling partners of levels 1 and 2 sit in the same lane (no DPP); only level 3 needs one lane exchange.
-// 60 store instructions per wave instead of 170.  Needs w % 4 == 0 (every configuration of BASELINE.json); odd widths
-// take the dword path.
-constexpr int kTrStride = 36;
-constexpr int kTrTile = 32 * kTrStride;                   // floats per transposed tile
-typedef unsigned int st_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int st_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack_h2(float a, float b) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 v;
-    v[0] = (_Float16)a;
-    v[1] = (_Float16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-
-template <bool kGuard, typename OutT>
-__device__ __forceinline__ void pyramid_store_vec(const BuildArgs& g, f32x16 (&acc)[PR], int b, int pair, int m0, int wave,
-                                                  int py0, int px0, int lane, float* scratch) {
-    constexpr int ES = sizeof(OutT);
-    OutT* const lv0 = reinterpret_cast<OutT*>(g.lvl[0]);
-    OutT* const lv1 = reinterpret_cast<OutT*>(g.lvl[1]);
-    OutT* const lv2 = reinterpret_cast<OutT*>(g.lvl[2]);
-    OutT* const lv3 = reinterpret_cast<OutT*>(g.lvl[3]);
-    const int khalf = lane >> 5, l31 = lane & 31;
-    const int rrow = lane >> 3, xq = (lane & 7) * 4;        // read-back coordinates: source row rrow + 8q, columns xq..xq+3
-    const int P0 = g.hl[0] * g.wl[0], P1 = g.hl[1] * g.wl[1], P2 = g.hl[2] * g.wl[2], P3 = g.hl[3] * g.wl[3];
-    const int i0 = m0 + wave * 32;
-    const int64_t row0 = (int64_t)b * g.N + i0;
-    constexpr int kSpan = 0x7ffffff0, kDrop = (int)0x80000000u;
-    const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(
-        lv0 + pair * g.lvl_pair_stride[0] + row0 * P0 + py0 * g.wl[0] + px0, 0, kSpan, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
-        lv1 + pair * g.lvl_pair_stride[1] + row0 * P1 + (py0 >> 1) * g.wl[1] + (px0 >> 1), 0, kSpan, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(
-        lv2 + pair * g.lvl_pair_stride[2] + row0 * P2 + (py0 >> 2) * g.wl[2] + (px0 >> 2), 0, kSpan, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r3 = __builtin_amdgcn_make_buffer_rsrc(
-        lv3 + pair * g.lvl_pair_stride[3] + row0 * P3 + (py0 >> 3) * g.wl[3] + (px0 >> 3), 0, kSpan, 0x00020000);
-    const int x = px0 + xq;                                 // first of this lane's four columns (w % 4 == 0: all in or all out)
-    const int co0 = (!kGuard || x < g.wl[0]) ? xq * ES : kDrop;
-    const int co1 = (!kGuard || (x >> 1) < g.wl[1]) ? (xq >> 1) * ES : kDrop;
-    const int co2 = (!kGuard || (x >> 2) < g.wl[2]) ? (xq >> 2) * ES : kDrop;
-    const int co3 = (!kGuard || (x >> 3) < g.wl[3]) ? (xq >> 3) * ES : kDrop;
-#ifndef SF_CORR_NT
-#define SF_CORR_NT 2
-#endif
-#ifndef SF_CORR_PACK
-#define SF_CORR_PACK 1      // fp16 level-0 cells leave as packed pairs (A/B knob)
-#endif
-    constexpr int kNt = SF_CORR_NT;
-    float l2s[PR / 4][4];                                       // level-2 values (one per lane and source row)
-#pragma unroll
-    for (int t2 = 0; t2 < PR / 4; ++t2) {
-        float l1s[4];                                           // sum of the two level-1 values of the first row pair
-#pragma unroll
-        for (int u2 = 0; u2 < 2; ++u2) {
-            const int tp = 2 * t2 + u2;
-            // ---- transpose patch rows 2tp, 2tp+1 (a wave's DS operations execute in order: no barrier) ----
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    scratch[u * kTrTile + ((r & 3) + 8 * (r >> 2) + 4 * khalf) * kTrStride + l31] = acc[2 * tp + u][r] * g.scale;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int rr = rrow + 8 * q;
-                const bool iok = !kGuard || (i0 + rr < g.N);
-                const float4 a = *reinterpret_cast<const float4*>(scratch + rr * kTrStride + xq);
-                const float4 c = *reinterpret_cast<const float4*>(scratch + kTrTile + rr * kTrStride + xq);
-                const bool ok0 = !kGuard || (iok && py0 + 2 * tp < g.hl[0]);
-                const bool ok1 = !kGuard || (iok && py0 + 2 * tp + 1 < g.hl[0]);
-                const int so = (rr * P0 + 2 * tp * g.wl[0]) * ES;
-                if constexpr (ES == 4) {
-                    st_u32x4 va, vc;
-                    va[0] = __builtin_bit_cast(unsigned, a.x); va[1] = __builtin_bit_cast(unsigned, a.y);
-                    va[2] = __builtin_bit_cast(unsigned, a.z); va[3] = __builtin_bit_cast(unsigned, a.w);
-                    vc[0] = __builtin_bit_cast(unsigned, c.x); vc[1] = __builtin_bit_cast(unsigned, c.y);
-                    vc[2] = __builtin_bit_cast(unsigned, c.z); vc[3] = __builtin_bit_cast(unsigned, c.w);
-                    __builtin_amdgcn_raw_buffer_store_b128(va, r0, ok0 ? co0 : kDrop, so, kNt);
-                    __builtin_amdgcn_raw_buffer_store_b128(vc, r0, ok1 ? co0 : kDrop, so + g.wl[0] * ES, kNt);
-                } else {
-                    st_u32x2 va, vc;
-                    va[0] = pack_h2(a.x, a.y); va[1] = pack_h2(a.z, a.w);
-                    vc[0] = pack_h2(c.x, c.y); vc[1] = pack_h2(c.z, c.w);
-                    __builtin_amdgcn_raw_buffer_store_b64(va, r0, ok0 ? co0 : kDrop, so, kNt);
-                    __builtin_amdgcn_raw_buffer_store_b64(vc, r0, ok1 ? co0 : kDrop, so + g.wl[0] * ES, kNt);
-                }
-                // level 1: 2x2 means of (patch rows 2tp, 2tp+1) x (columns 0-1, 2-3)
-                const float p0 = 0.25f * ((a.x + c.x) + (a.y + c.y)), p1 = 0.25f * ((a.z + c.z) + (a.w + c.w));
-                const bool ok = !kGuard || (iok && (py0 >> 1) + tp < g.hl[1]);
-                const int s1 = (rr * P1 + tp * g.wl[1]) * ES;
-                if constexpr (ES == 4) {
-                    st_u32x2 v;
-                    v[0] = __builtin_bit_cast(unsigned, p0);
-                    v[1] = __builtin_bit_cast(unsigned, p1);
-                    __builtin_amdgcn_raw_buffer_store_b64(v, r1, ok ? co1 : kDrop, s1, 0);
-                } else {
-                    __builtin_amdgcn_raw_buffer_store_b32(pack_h2(p0, p1), r1, ok ? co1 : kDrop, s1, 0);
-                }
-                // level 2: mean of the four level-1 cells of patch rows 4 t2 .. 4 t2 + 3
-                if (u2 == 0) l1s[q] = p0 + p1;
-                else {
-                    l2s[t2][q] = 0.25f * (l1s[q] + (p0 + p1));
-                    const bool ok2 = !kGuard || (iok && (py0 >> 2) + t2 < g.hl[2]);
-                    store_cell<OutT, 0>(l2s[t2][q], r2, ok2 ? co2 : kDrop, (rr * P2 + t2 * g.wl[2]) * ES);
-                }
-            }
-        }
-    }
-    // ---- level 3: the two level-2 rows of this lane and of the neighbouring column quad ----
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int rr = rrow + 8 * q;
-        const float s3 = l2s[0][q] + l2s[1][q];
-        const float l3 = 0.25f * (s3 + dpp_xor1(s3));
-        const bool ok = (lane & 1) == 0 && (!kGuard || (i0 + rr < g.N && (py0 >> 3) < g.hl[3]));
-        store_cell<OutT, 0>(l3, r3, ok ? co3 : kDrop, (rr * P3) * ES);
-    }
-}
-
-// scratch: per-wave LDS region of 2 * kTrTile floats (the main-loop buffers, after a workgroup barrier), or nullptr.
-template <typename OutT = float, bool kVec = false>
+// (A vector store side for w % 4 == 0 -- every pair of patch rows transposed through a per-wave LDS scratch so that level 0
+// leaves as 16-byte / 8-byte stores, 60 store instructions per wave instead of 170 -- measured SLOWER on MI355X (r02): fp16
+// build 2.20 vs 1.68 ms, f16x3 build 3.03 vs 2.34 ms per 24 images, with 24 / 28 bytes per lane of scratch memory.  The
+// build is not bound by the number of store instructions; removed.)
+template <typename OutT = float>
 __device__ __forceinline__ void pyramid_epilogue(const BuildArgs& g, f32x16 (&acc)[PR], int b, int pair, int m0, int wave,
-                                                 int py0, int px0, int lane, float* scratch = nullptr) {
+                                                 int py0, int px0, int lane) {
     const bool interior = m0 + BM <= g.N && py0 + PR <= g.hl[0] && px0 + PC <= g.wl[0] &&
                           (py0 >> 1) + PR / 2 <= g.hl[1] && (py0 >> 2) + PR / 4 <= g.hl[2] && (py0 >> 3) < g.hl[3] &&
                           ((px0 + PC) >> 1) <= g.wl[1] && ((px0 + PC) >> 2) <= g.wl[2] && ((px0 + PC) >> 3) <= g.wl[3];
-    if constexpr (kVec) {                    // one flavour per kernel instantiation: both inlined cost registers (spills)
-        if (interior) pyramid_store_vec<false, OutT>(g, acc, b, pair, m0, wave, py0, px0, lane, scratch);
-        else pyramid_store_vec<true, OutT>(g, acc, b, pair, m0, wave, py0, px0, lane, scratch);
-    } else {
-        if (interior) pyramid_store<false, OutT>(g, acc, b, pair, m0, wave, py0, px0, lane);
-        else pyramid_store<true, OutT>(g, acc, b, pair, m0, wave, py0, px0, lane);
-    }
+    if (interior) pyramid_store<false, OutT>(g, acc, b, pair, m0, wave, py0, px0, lane);
+    else pyramid_store<true, OutT>(g, acc, b, pair, m0, wave, py0, px0, lane);
 }
 
 __global__ __launch_bounds__(kThreads, 2) void corr_build_kernel(const BuildArgs g) {
@@ -515,11 +379,7 @@ __global__ __launch_bounds__(256) void split_pack_kernel(const float* f1, const 
 
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
-#ifndef SF_CORR_VEC_WAVES
-#define SF_CORR_VEC_WAVES 3      // waves per SIMD the kVec = true forms are compiled for (3: 168 registers, 6-7 of them spilled; 2: none)
-#endif
-template <bool kVec>
-__global__ __launch_bounds__(kThreads, NSTAGE == 2 ? (kVec ? SF_CORR_VEC_WAVES : 3) : 2) void corr_build_dma_kernel(const BuildArgs g, const char* ws, int Dp) {
+__global__ __launch_bounds__(kThreads, NSTAGE == 2 ? 3 : 2) void corr_build_dma_kernel(const BuildArgs g, const char* ws, int Dp) {
     using namespace sf_split;
     __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -582,9 +442,7 @@ __global__ __launch_bounds__(kThreads, NSTAGE == 2 ? (kVec ? SF_CORR_VEC_WAVES :
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
         }
     }
-    if (kVec) __syncthreads();                                   // the stage buffers become the transpose scratch
-    pyramid_epilogue<float, kVec>(g, acc, b, pair, m0, wave, py0, px0, lane,
-                                  reinterpret_cast<float*>(smem) + wave * 2 * kTrTile);
+    pyramid_epilogue<float>(g, acc, b, pair, m0, wave, py0, px0, lane);
 }
 
 // ---- fp16 build (SF_PRECISION_F16): single f16 product, fp32 accumulation, volume stored as IEEE fp16 ------------
@@ -612,14 +470,9 @@ __global__ __launch_bounds__(256) void pack_f16_kernel(const float* f1, const fl
     *reinterpret_cast<f16x8*>(ws + (int64_t)blockIdx.z * plane + ((int64_t)kq * N + px) * 16) = h;
 }
 
-template <bool kVec>
-__global__ __launch_bounds__(kThreads, kVec ? SF_CORR_VEC_WAVES : 3) void corr_build_f16_kernel(const BuildArgs g, const char* ws, int Dp) {
+__global__ __launch_bounds__(kThreads, 3) void corr_build_f16_kernel(const BuildArgs g, const char* ws, int Dp) {
     using namespace sf_split;
     __shared__ __attribute__((aligned(1024))) char smem[2 * FSTAGE];
-#ifdef SF_CORR_TIMERS
-    const long long ts0 = __builtin_readcyclecounter();
-    const long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, l31 = lane & 31;
@@ -673,19 +526,7 @@ __global__ __launch_bounds__(kThreads, kVec ? SF_CORR_VEC_WAVES : 3) void corr_b
             }
         }
     }
-#ifdef SF_CORR_TIMERS
-    const long long ts1 = __builtin_readcyclecounter();
-#endif
-    if (kVec) __syncthreads();                                   // the stage buffers become the transpose scratch
-    pyramid_epilogue<_Float16, kVec>(g, acc, b, pair, m0, wave, py0, px0, lane,
-                                     reinterpret_cast<float*>(smem) + wave * 2 * kTrTile);
-#ifdef SF_CORR_TIMERS
-    if (g.ts && tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        long long* d = g.ts + (int64_t)blockIdx.x * 8;
-        d[0] = ts0; d[1] = ts1; d[2] = __builtin_readcyclecounter(); d[3] = rt0; d[4] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
+    pyramid_epilogue<_Float16>(g, acc, b, pair, m0, wave, py0, px0, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -986,23 +827,6 @@ extern "C" int sf_corr_build_pyramid_pitched(const float* f1, const float* f2, i
               ((reinterpret_cast<uintptr_t>(f2) & 15) == 0);
     dim3 grid(g.pcols * sf::ceil_div(h, PR), sf::ceil_div(g.N, BM), B * pairs);
     g.np = (int)grid.x; g.mt = (int)grid.y;
-#ifdef SF_CORR_TIMERS
-    g.ts = getenv("SF_CORR_TS_BUF") ? (long long*)strtoull(getenv("SF_CORR_TS_BUF"), nullptr, 0) : nullptr;
-#endif
-    {
-        bool al = (w % 4 == 0);
-        for (int l = 0; l < 4; ++l) {
-            al = al && (reinterpret_cast<uintptr_t>(g.lvl[l]) & 15) == 0;
-            if (pairs > 1) al = al && ((g.lvl_pair_stride[l] * (precision == SF_PRECISION_F16 ? 2 : 4)) & 15) == 0;
-        }
-        // measured on MI355X (r02): the transposed 16-byte epilogue is SLOWER than the dword one (fp16 build 2.20 vs
-        // 1.68 ms, f16x3 build 3.03 vs 2.34 ms per 24 images) -- the build is not bound by store-instruction count.
-        // Kept as a compile-time experiment (-DSF_CORR_VEC=1 through tools/build_variant.sh); see DESIGN.md.
-#ifndef SF_CORR_VEC
-#define SF_CORR_VEC 0
-#endif
-        g.vec_store = (al && SF_CORR_VEC == 1) ? 1 : 0;
-    }
     // patches per L2-resident block: ~1.75 MB of packed target features (of the 4 MiB L2 of an XCD)
     const int patch_bytes = BN * Dp * (precision == SF_PRECISION_F16 ? 2 : 4);
     g.pblk = (7 << 18) / patch_bytes;
@@ -1012,21 +836,13 @@ extern "C" int sf_corr_build_pyramid_pitched(const float* f1, const float* f2, i
     if (precision == SF_PRECISION_F16X3) {
         hipLaunchKernelGGL(split_pack_kernel, dim3(sf::ceil_div(g.N, 256), Dp / 8, 2 * B * pairs), dim3(256), 0,
                            (hipStream_t)stream, f1, f2, f_clip_stride, f_pair_stride, (char*)split_ws, pairs, D, Dp, g.N);
-        if (g.vec_store)
-            hipLaunchKernelGGL(corr_build_dma_kernel<true>, dim3((unsigned)n_wg), dim3(kThreads), 0, (hipStream_t)stream, g,
-                               (const char*)split_ws, Dp);
-        else
-            hipLaunchKernelGGL(corr_build_dma_kernel<false>, dim3((unsigned)n_wg), dim3(kThreads), 0, (hipStream_t)stream, g,
-                               (const char*)split_ws, Dp);
+        hipLaunchKernelGGL(corr_build_dma_kernel, dim3((unsigned)n_wg), dim3(kThreads), 0, (hipStream_t)stream, g,
+                           (const char*)split_ws, Dp);
     } else if (precision == SF_PRECISION_F16) {
         hipLaunchKernelGGL(pack_f16_kernel, dim3(sf::ceil_div(g.N, 256), Dp / 8, 2 * B * pairs), dim3(256), 0,
                            (hipStream_t)stream, f1, f2, f_clip_stride, f_pair_stride, (char*)split_ws, pairs, D, Dp, g.N);
-        if (g.vec_store)
-            hipLaunchKernelGGL(corr_build_f16_kernel<true>, dim3((unsigned)n_wg), dim3(kThreads), 0, (hipStream_t)stream, g,
-                               (const char*)split_ws, Dp);
-        else
-            hipLaunchKernelGGL(corr_build_f16_kernel<false>, dim3((unsigned)n_wg), dim3(kThreads), 0, (hipStream_t)stream, g,
-                               (const char*)split_ws, Dp);
+        hipLaunchKernelGGL(corr_build_f16_kernel, dim3((unsigned)n_wg), dim3(kThreads), 0, (hipStream_t)stream, g,
+                           (const char*)split_ws, Dp);
     } else
         hipLaunchKernelGGL(corr_build_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, g);
     return sf::check_launch("sf_corr_build_pyramid");

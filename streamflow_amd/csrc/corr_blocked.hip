@@ -23,7 +23,6 @@
 // The lookup's product is the fp16 k-octet image of the 324 correlation features (SF_LAYOUT_F16_KOCT), i.e. the LDS
 // image of the first GEMM of the correlation encoder; fp32 planes are optional (API parity / tests).
 #include "sf_common.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -95,17 +94,12 @@ struct BuildArgs {
     const char* ws;               // packed features: image (img, side) = [KD / 8][Np][8] halves, pixel N.. = zeros
     char* vol;
     int64_t vol_img_stride;       // bytes
-    int n_img, h, w, N, Np;
+    int h, w, N, Np;
     int pairs, shared;            // shared: packed planes are per frame (see pack_f16z_kernel)
     VolGeom g;
-    // target patches: np16 patches of 16 rows x 16 columns (two block rows x two blocks) cover block rows 0 .. 2 * rows16 - 1;
-    // an odd last block row is covered by np32 patches of 8 rows x 32 columns
-    int pcols16, np16, pcols32, np32, rows16;
+    int pcols, np;                // target patches of 8 rows x 32 columns: per block row, per image
     int ntiles, nchunks, tpc;     // 32-source tiles per image, chunks per image, tiles per chunk
     float scale;                  // applied in the epilogue (1 when folded into the packed source features)
-#ifdef SF_CORR_TIMERS
-    long long* ts;
-#endif
 };
 
 // features fp32 [D][N] -> fp16 k-octet planes [(k / 8)][Np][8]; pixels N .. Np-1 are zero (the target of every patch
@@ -179,35 +173,23 @@ __global__ __launch_bounds__(256) void pack_f16z4_kernel(const float* f1, const 
 //  * The A fragments of the NEXT tile are requested before the epilogue's stores: vmcnt retires in issue order, so a load
 //    issued behind the 32 stores of a tile would wait for their HBM acknowledgement (~16k cycles when the chip writes at
 //    full rate) -- the first version of this kernel did, and its waves spent as long draining as computing.
-//  * kShape16: the patch is 16 rows x 16 columns, lane = (block row l31 >> 4, column l31 & 15), so that a tile produces a
-//    COMPLETE 8 x 8 level-1 block (a full 128-byte line).  With 8 x 32 patches the level-1 cells of a block come from two
-//    work items at different times: partial-line writes, which HBM3 (no data mask) serves as read-modify-write -- the
-//    store-only rate of that pattern measured 3.9 TB/s against 5.5 for full lines.  8 x 32 is used for an odd last block
-//    row only (no wasted MFMA rows).
+//  * With 8 x 32 patches the level-1 cells of a block come from two work items at different times: partial-line writes,
+//    which HBM3 (no data mask) serves as read-modify-write (store-only: 3.9 TB/s against 5.5 for full lines).  16 x 16 patches for the even block rows (a tile then produces a
+//    COMPLETE 8 x 8 level-1 block, a full 128-byte line) measured slower than 8 x 32 everywhere all the same (Sintel 1177
+//    vs 1131 us) and were removed.
 // (History: the first blocked kernel kept round 2's structure -- 128 x 256 tile per workgroup, both operands staged
 // through a 2- or 3-stage LDS ring -- and measured 27k cycles of k-loop per tile of which 4.1k were MFMA issue: every
 // wave sat ~190 cycles in each of its 48 LDS-DMA instructions and ~0.5k cycles per stage at the barrier; interleaving the
 // DMA instructions with the MFMAs moved that time, it did not remove it.  DESIGN.md section 10.)
-#ifdef SF_CORR_TIMERS
-#define SF_TIMER_ARGS , long long& t_load, long long& t_k, long long& t_e, int& n_t
-#define SF_TIMER_PASS , t_load, t_k, t_e, n_t
-#else
-#define SF_TIMER_ARGS
-#define SF_TIMER_PASS
-#endif
-template <bool kShape16, bool kScale>
-__device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int item SF_TIMER_ARGS) {
-#ifdef SF_CORR_TIMERS
-    const long long ts0 = __builtin_readcyclecounter();
-#endif
+template <bool kScale>
+__device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int item) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int khalf = lane >> 5, l31_ = lane & 31;
     // item order [image][chunk][patch]: the workgroups that run side by side on an XCD share the chunk's source features
-    const int np = kShape16 ? g.np16 : g.np32, pcols = kShape16 ? g.pcols16 : g.pcols32;
-    const int patch = item % np, chunk = (item / np) % g.nchunks, img = item / (np * g.nchunks);
-    // patch origin in blocks: kShape16: block rows 2 pyb, 2 pyb + 1, blocks 2 pxb, 2 pxb + 1; else block row pyb, blocks 4 pxb ..
-    const int pyb = kShape16 ? patch / pcols : 2 * g.rows16 + patch / pcols, pxb = patch % pcols;
+    const int patch = item % g.np, chunk = (item / g.np) % g.nchunks, img = item / (g.np * g.nchunks);
+    // patch origin in blocks: block row pyb, blocks 4 pxb ..
+    const int pyb = patch / g.pcols, pxb = patch % g.pcols;
     const int plane = (KD / 8) * g.Np * 16;                       // bytes of one packed image (< 2 GiB, host-checked)
     const int pa = g.shared ? (img / g.pairs) * (g.pairs + 1) + img % g.pairs : 2 * img;    // packed plane of the source side
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
@@ -222,8 +204,7 @@ __device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int i
     // w, w + 8, ...: always cell group w % 4.  Cells outside the image read the zero pixel. ----
     {
         const int cell = (wave & 3) * 64 + lane, t = cell >> 5, l = cell & 31;
-        const int ty = kShape16 ? 16 * pyb + 8 * (l >> 4) + t : 8 * pyb + t;
-        const int tx = kShape16 ? 16 * pxb + (l & 15) : 32 * pxb + l;
+        const int ty = 8 * pyb + t, tx = 32 * pxb + l;
         const int vob = ((ty < g.h && tx < g.w) ? ty * g.w + tx : g.N) * 16;
         static_assert(NW % 4 == 0, "a wave keeps its cell group");
         for (int p = wave; p < (KD / 8) * 4; p += NW)
@@ -235,19 +216,10 @@ __device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int i
     // trip of the tile loop -- i.e. a full drain of the previous tile's stores at the top of each tile.)
     __builtin_amdgcn_s_waitcnt(0x0070);                           // vmcnt(0) expcnt(7) lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
-#ifdef SF_CORR_TIMERS
-    const long long ts1 = __builtin_readcyclecounter();
-    t_load += ts1 - ts0;
-#endif
     const int rec = g.g.rec;
     char* const img_base = g.vol + (int64_t)img * g.vol_img_stride;
     const char* const sbB = smem + (khalf * BN + l31_) * 16;      // + (2 ks * 256 + t * 32) * 16
     constexpr int kSteps = KD / 16;
-#if defined(SF_CORRB_ABLATE) && SF_CORRB_ABLATE == 2      // timing ablation: four k-steps only
-    constexpr int kRun = 4;
-#else
-    constexpr int kRun = kSteps;
-#endif
     auto grab = [&]() {
         int t = 0;
         if (lane == 0) t = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -256,9 +228,6 @@ __device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int i
     int tile = grab();
     if (tile >= t_count) return;
     for (;;) {
-#ifdef SF_CORR_TIMERS
-        const long long tt0 = __builtin_readcyclecounter();
-#endif
         const int next = grab();                                  // (LDS atomic: its latency hides behind the k-loop)
         const int i0 = (t_begin + tile) * 32;                     // first source pixel of this tile
         // A fragment of k-step ks: k-octet 2 ks + khalf of source pixel i0 + l31 (pixels past N clamped: padding records);
@@ -276,33 +245,30 @@ __device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int i
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 #pragma unroll
-        for (int ks = 0; ks < kRun; ++ks) {
+        for (int ks = 0; ks < kSteps; ++ks) {
             const f16x8 a = __builtin_bit_cast(f16x8, af[ks % kRing]);
 #pragma unroll
             for (int t = 0; t < PR; ++t) {
                 const f16x8 bv = *reinterpret_cast<const f16x8*>(sbB + (ks * 2 * BN + t * PC) * 16);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bv, acc[t], 0, 0, 0);
             }
-            if (ks + kRing < kRun) af[ks % kRing] = __builtin_amdgcn_raw_buffer_load_b128(ra, voa, (ks + kRing) * 2 * kq_step, 0);
+            if (ks + kRing < kSteps) af[ks % kRing] = __builtin_amdgcn_raw_buffer_load_b128(ra, voa, (ks + kRing) * 2 * kq_step, 0);
         }
         // Issue order of the whole (fully unrolled) k-loop, pinned: the ring's loads first, then B fragment reads running
         // kAhead MFMAs ahead of their use, one A refill behind every eighth MFMA.  Left to itself hipcc sinks every load
         // next to its use (vmcnt(0) / lgkmcnt(0) in front of each MFMA: 28k cycles per tile for 4.1k of MFMA issue).
         {
-            constexpr int kAhead = (NW <= 8) ? 8 : 3, kMfma = kRun * PR;
+            constexpr int kAhead = (NW <= 8) ? 8 : 3, kMfma = kSteps * PR;
             __builtin_amdgcn_sched_group_barrier(0x020, kRing, 0);               // VMEM reads
             __builtin_amdgcn_sched_group_barrier(0x100, kAhead, 0);              // DS reads
 #pragma unroll
             for (int i = 0; i < kMfma; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);               // one MFMA
                 if (i + kAhead < kMfma) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if (i % PR == PR - 1 && i / PR + kRing < kRun) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                if (i % PR == PR - 1 && i / PR + kRing < kSteps) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifdef SF_CORR_TIMERS
-        const long long tt1 = __builtin_readcyclecounter();
-#endif
         // ---- epilogue.  C/D layout: lane = (MFMA column l31, k-half), register r = source row (r&3) + 8(r>>2) + 4 khalf,
         // acc[t] = row t of the lane's block row: a lane's eight values of one register are one block column of level 0.
         // Per-lane store offsets are recomputed per tile from a laundered lane id: as loop invariants they would occupy
@@ -310,39 +276,29 @@ __device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int i
         int l31 = l31_;
         asm volatile("" : "+v"(l31));
         const int rowh = 4 * khalf * rec;
-        const int br = kShape16 ? l31 >> 4 : 0, c = kShape16 ? l31 & 15 : l31;     // block row of the lane, column in the patch
-        const int by0 = kShape16 ? 2 * pyb + br : pyb, bxp = kShape16 ? 2 * pxb : 4 * pxb;   // level-0 block row / first block
+        const int c = l31;                                     // column in the patch
+        const int by0 = pyb, bxp = 4 * pxb;                     // level-0 block row / first block
         // level 0: lanes of one block row = consecutive 16-byte block columns (256 or 512 contiguous bytes per source row)
-        const int vo0_ = (by0 < g.g.nby[0] && bxp + (c >> 3) < g.g.nbx[0])
+        const int vo0 = (by0 < g.g.nby[0] && bxp + (c >> 3) < g.g.nbx[0])
                              ? rowh + g.g.off[0] + (by0 * g.g.nbx[0] + bxp) * 128 + c * 16 : kDrop;
         // level 1: lane pair (2j, 2j+1) holds level-1 column j, four rows (block row by0: rows 4 (by0 & 1) .. +3 of level-1
         // block row by0 >> 1): an 8-byte piece; lane parity k1 stores source row (2 jp + k1) of a register pair.
-        // kShape16: the two block rows of the patch supply both halves of every block column: 128 full bytes per source row.
         const int j1 = c >> 1, k1 = c & 1;
         const int by1 = by0 >> 1, bx1 = (bxp >> 1) + (j1 >> 3);
-        const int vo1_ = (by1 < g.g.nby[1] && bx1 < g.g.nbx[1])
+        const int vo1 = (by1 < g.g.nby[1] && bx1 < g.g.nbx[1])
                              ? rowh + k1 * rec + g.g.off[1] + (by1 * g.g.nbx[1] + bx1) * 128 + (j1 & 7) * 16 + (by0 & 1) * 8 : kDrop;
         // level 2: lane quad = level-2 column (bxp * 2 + (c >> 2)), rows 2 (by0 & 3) .. +1 of block row by0 >> 2 (4 bytes);
         // lane k2 of the quad stores source row k2 of a register group
         const int k2 = c & 3, tx2 = bxp * 2 + (c >> 2);
         const int by2 = by0 >> 2;
-        const int vo2_ = (by2 < g.g.nby[2] && (tx2 >> 3) < g.g.nbx[2])
+        const int vo2 = (by2 < g.g.nby[2] && (tx2 >> 3) < g.g.nbx[2])
                              ? rowh + k2 * rec + g.g.off[2] + (by2 * g.g.nbx[2] + (tx2 >> 3)) * 128 + (tx2 & 7) * 16 + (by0 & 3) * 4 : kDrop;
         // level 3: lanes 0..3 of an octet hold level-3 column bxp + (c >> 3), row by0 & 7 of block row by0 >> 3 (2 bytes)
         const int k3 = c & 7, tx3 = bxp + (c >> 3);
         const int by3 = by0 >> 3;
-        const int vo3_ = (k3 < 4 && by3 < g.g.nby[3] && (tx3 >> 3) < g.g.nbx[3])
+        const int vo3 = (k3 < 4 && by3 < g.g.nby[3] && (tx3 >> 3) < g.g.nbx[3])
                              ? rowh + k3 * rec + g.g.off[3] + (by3 * g.g.nbx[3] + (tx3 >> 3)) * 128 + (tx3 & 7) * 16 + (by0 & 7) * 2 : kDrop;
         constexpr int kNt = SF_CORRB_NT;
-#if defined(SF_CORRB_ABLATE) && SF_CORRB_ABLATE == 1      // timing ablation: no stores leave the CU
-        const int vo0 = kDrop | (vo0_ & 0), vo1 = kDrop | (vo1_ & 0), vo2 = kDrop | (vo2_ & 0), vo3 = kDrop | (vo3_ & 0);
-#elif defined(SF_CORRB_ABLATE) && SF_CORRB_ABLATE == 3    // only the level-0 stores leave the CU
-        const int vo0 = vo0_, vo1 = kDrop | (vo1_ & 0), vo2 = kDrop | (vo2_ & 0), vo3 = kDrop | (vo3_ & 0);
-#elif defined(SF_CORRB_ABLATE) && SF_CORRB_ABLATE == 4    // only the pooled levels' stores leave the CU
-        const int vo0 = kDrop | (vo0_ & 0), vo1 = vo1_, vo2 = vo2_, vo3 = vo3_;
-#else
-        const int vo0 = vo0_, vo1 = vo1_, vo2 = vo2_, vo3 = vo3_;
-#endif
         const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(img_base + (int64_t)i0 * rec, 0, 32 * rec, 0x00020000);
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {                       // register group: source rows 8 rq + 4 khalf + (0..3)
@@ -391,9 +347,6 @@ __device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int i
             const _Float16 h3 = (_Float16)sel3;
             __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, h3), rv, vo3, (8 * rq) * rec, 0);
         }
-#ifdef SF_CORR_TIMERS
-        t_k += tt1 - tt0; t_e += __builtin_readcyclecounter() - tt1; ++n_t;
-#endif
         if (next >= t_count) break;
         tile = next;
     }
@@ -401,28 +354,10 @@ __device__ __forceinline__ void build_item(const BuildArgs& g, char* smem, int i
 
 // One workgroup per work item.  (A persistent form -- one workgroup per CU looping over items -- measured the same
 // 1.13 ms and, inlined into that loop, hipcc no longer honours the pinned issue order of the k-loop: DESIGN.md section 10.)
-template <bool kScale, bool kMixed>
+template <bool kScale>
 __global__ __launch_bounds__(kBuildThreads, NW / 4) void corr_build_blocked_kernel(const BuildArgs g) {
     __shared__ __attribute__((aligned(1024))) char smem[kPatchBytes + 16];
-#ifdef SF_CORR_TIMERS
-    const long long ts0 = __builtin_readcyclecounter();
-    const long long rt0 = __builtin_amdgcn_s_memrealtime();
-    long long t_load = 0, t_k = 0, t_e = 0;
-    int n_t = 0;
-#endif
-    // 16 x 16 patches first (if any), then the 8 x 32 patches
-    const int n16 = g.np16 * g.nchunks * g.n_img;                 // workgroup-uniform
-    const int id = sf::xcd_linear_id(blockIdx.x, gridDim.x);
-    if (kMixed && id < n16) build_item<true, kScale>(g, smem, id SF_TIMER_PASS);
-    else build_item<false, kScale>(g, smem, id - n16 SF_TIMER_PASS);
-#ifdef SF_CORR_TIMERS
-    if (g.ts && (threadIdx.x & 63) == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        long long* d = g.ts + ((int64_t)blockIdx.x * NW + (threadIdx.x >> 6)) * 8;
-        d[0] = ts0; d[1] = t_load; d[2] = __builtin_readcyclecounter(); d[3] = rt0; d[4] = __builtin_amdgcn_s_memrealtime();
-        d[5] = t_k; d[6] = t_e; d[7] = n_t;
-    }
-#endif
+    build_item<kScale>(g, smem, sf::xcd_linear_id(blockIdx.x, gridDim.x));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -432,9 +367,6 @@ constexpr int LP = 32;                          // source pixels per workgroup
 constexpr int NCH = 324, NOCT = 41;
 constexpr int TROW = NOCT * 8;                  // halves per pixel in the transpose buffer (656 bytes: 16-byte aligned rows,
                                                 // 164 dwords = 36 mod 64: the 16-byte read-back of 16 pixels is conflict-free)
-#ifndef SF_LOOKB_W2_ALWAYS
-#define SF_LOOKB_W2_ALWAYS 0
-#endif
 #ifndef SF_LOOKB_STREAM_BYTES
 // Volumes of at least this size are read with the streaming cache policy (slc): every line of a footprint is used once per lookup.
 // Alone (bench.py --corr-only: 15 lookups back to back) that pays from ~2.5 GB on -- Sintel, 24 images = 3.3 GB: 78-81 -> 66-69 us per
@@ -522,12 +454,9 @@ __global__ __launch_bounds__(kThreads, SF_LOOKB_WAVES) void corr_lookup_blocked_
         f.w0 = __builtin_amdgcn_raw_buffer_load_b128(rv, piece(0), 0, AUX);
         f.w1 = __builtin_amdgcn_raw_buffer_load_b128(rv, piece(1), 0, AUX);
         // rows 16, 17 (a third block row) are part of the footprint only when ys % 8 == 7: requested only then -- an unconditional
-        // 4-byte request pulled two more 128-byte lines per level into L2 for seven footprints of eight (round 5)
-#if SF_LOOKB_W2_ALWAYS
-        f.w2 = __builtin_amdgcn_raw_buffer_load_b32(rv, piece(2), 0, AUX);
-#else
+        // 4-byte request pulled two more 128-byte lines per level into L2 for seven footprints of eight (round 5: 100 -> 85 us per
+        // lookup, profiles/r05_lookup_third_row_ab.txt)
         f.w2 = __builtin_amdgcn_raw_buffer_load_b32(rv, ((ys & 7) == 7) ? piece(2) : kDrop, 0, AUX);
-#endif
         return f;
     };
 
@@ -678,15 +607,9 @@ extern "C" int sf_corr_build_blocked(const float* f1, const float* f2, int64_t f
     g.ws = static_cast<const char*>(ws);
     g.vol = static_cast<char*>(vol);
     g.vol_img_stride = vol_img_stride_bytes;
-    g.n_img = n_img; g.h = h; g.w = w;
-#ifndef SF_CORRB_SHAPE16
-#define SF_CORRB_SHAPE16 0       // 1: 16 x 16 patches for the even block rows (full-line level-1 writes, 256-byte level-0 runs).
-#endif                           // Measured slower than 8 x 32 everywhere (Sintel 1177 vs 1131 us): off.
-    g.rows16 = SF_CORRB_SHAPE16 ? g.g.nby[0] / 2 : 0;             // full pairs of block rows
-    g.pcols16 = sf::ceil_div(w, 16);
-    g.np16 = g.rows16 * g.pcols16;
-    g.pcols32 = sf::ceil_div(w, 32);
-    g.np32 = (g.g.nby[0] - 2 * g.rows16) * g.pcols32;
+    g.h = h; g.w = w;
+    g.pcols = sf::ceil_div(w, 32);
+    g.np = g.g.nby[0] * g.pcols;
     g.ntiles = sf::ceil_div(g.N, 32);
     g.nchunks = sf::ceil_div(g.ntiles, kTilesPerItem);
     g.tpc = sf::ceil_div(g.ntiles, g.nchunks);
@@ -702,10 +625,7 @@ extern "C" int sf_corr_build_blocked(const float* f1, const float* f2, int64_t f
     const bool fold = g.shared ? root_pow2 : pow2;
     const float pre = !fold ? 1.0f : (g.shared ? root : scale);
     g.scale = fold ? 1.0f : scale;
-#ifdef SF_CORR_TIMERS
-    g.ts = getenv("SF_CORR_TS_BUF") ? (long long*)strtoull(getenv("SF_CORR_TS_BUF"), nullptr, 0) : nullptr;
-#endif
-    const int64_t n_items = (int64_t)(g.np16 + g.np32) * g.nchunks * n_img;
+    const int64_t n_items = (int64_t)g.np * g.nchunks * n_img;
     SF_REQUIRE(n_items < ((int64_t)1 << 31), "sf_corr_build_blocked: too many work items");
     const int64_t n_wg = n_items;
     const bool vec4 = (g.N & 3) == 0 && (g.Np & 3) == 0 && (f_clip_stride & 3) == 0 && (f_pair_stride & 3) == 0 &&
@@ -718,13 +638,8 @@ extern "C" int sf_corr_build_blocked(const float* f1, const float* f2, int64_t f
                            (hipStream_t)stream, f1, f2, f_clip_stride, f_pair_stride, (char*)ws, pairs, D, KD, g.N, g.Np, pre, g.shared);
     const dim3 grid((unsigned)n_wg), block(kBuildThreads);
     hipStream_t st = (hipStream_t)stream;
-    if (g.np16 > 0) {
-        if (fold) hipLaunchKernelGGL((corr_build_blocked_kernel<false, true>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((corr_build_blocked_kernel<true, true>), grid, block, 0, st, g);
-    } else {
-        if (fold) hipLaunchKernelGGL((corr_build_blocked_kernel<false, false>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((corr_build_blocked_kernel<true, false>), grid, block, 0, st, g);
-    }
+    if (fold) hipLaunchKernelGGL(corr_build_blocked_kernel<false>, grid, block, 0, st, g);
+    else hipLaunchKernelGGL(corr_build_blocked_kernel<true>, grid, block, 0, st, g);
     return sf::check_launch("sf_corr_build_blocked");
 }
 

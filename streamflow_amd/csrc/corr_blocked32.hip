@@ -190,11 +190,7 @@ __global__ __launch_bounds__(kThreads, SF_CORRB32_WGS) void corr_build_blocked32
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mt][t][r] = 0.f;
-#if defined(SF_CORRB32_ABLATE) && SF_CORRB32_ABLATE == 2     // timing ablation: one k-stage only (the epilogue alone)
-    const int nk = 1;
-#else
     const int nk = g.Dp / DK;
-#endif
     const int offa = (khalf * BM + wm * 64 + l31_) * 16;
     const int offb = 2 * ST_A + (khalf * BN + wn * 128 + l31_) * 16;
 #pragma unroll
@@ -207,15 +203,10 @@ __global__ __launch_bounds__(kThreads, SF_CORRB32_WGS) void corr_build_blocked32
         else if (NSTAGE == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         __builtin_amdgcn_s_barrier();                           // ... everyone's; and slot nxt (stage kt - 1) is no longer read
-#if !(defined(SF_CORRB32_ABLATE) && SF_CORRB32_ABLATE == 4)   // timing ablation 4: no operand loads after the prologue (+ no stores)
         if (kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1, nxt);
-#endif
         const char* sb = smem + cur * STAGE;
         cur = (cur == NSTAGE - 1) ? 0 : cur + 1;
         nxt = (nxt == NSTAGE - 1) ? 0 : nxt + 1;
-#if defined(SF_CORRB32_ABLATE) && SF_CORRB32_ABLATE == 5      // timing ablation 5: operand loads only, no fragment reads / MFMA (+ no stores)
-        continue;
-#endif
         f16x8 ah[MT], al[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -263,16 +254,6 @@ __global__ __launch_bounds__(kThreads, SF_CORRB32_WGS) void corr_build_blocked32
     const int k3 = c & 7, tx3 = tx0 >> 3, by3 = pyb >> 2;
     const int vo3 = (th == 0 && k3 < 4 && by3 < g.g.nby[3] && (tx3 >> 3) < g.g.nbx[3])
                         ? rowh + k3 * rec + g.g.off[3] + by3 * g.g.nbx[3] * 128 + tx3 * 16 + (pyb & 3) * 4 : kDrop;
-#if defined(SF_CORRB32_ABLATE) && (SF_CORRB32_ABLATE == 1 || SF_CORRB32_ABLATE >= 3)   // timing ablations: no pooled-level stores
-#define SF_VO(x) (kDrop | ((x) & 0))
-#else
-#define SF_VO(x) (x)
-#endif
-#if defined(SF_CORRB32_ABLATE) && (SF_CORRB32_ABLATE == 1 || SF_CORRB32_ABLATE >= 4)     // ... no store at all leaves the CU (the main loop alone)
-#define SF_VO0(x) (kDrop | ((x) & 0))
-#else
-#define SF_VO0(x) (x)
-#endif
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -291,7 +272,7 @@ __global__ __launch_bounds__(kThreads, SF_CORRB32_WGS) void corr_build_blocked32
                         v0[t] = acc[mt][t][r] * g.scale;
                         o0[t] = __builtin_bit_cast(unsigned, v0[t]);
                     }
-                    __builtin_amdgcn_raw_buffer_store_b128(o0, rv, SF_VO0(vo0), (32 * mt + ri + 8 * rq) * rec, 2);
+                    __builtin_amdgcn_raw_buffer_store_b128(o0, rv, vo0, (32 * mt + ri + 8 * rq) * rec, 2);
                     // (gfx950: a VALU write to the data registers of a > 64-bit buffer store with an SGPR soffset in the very next issue
                     // slots corrupts the stored data -- csrc/corr_blocked.hip; pad by hand, tied to the data registers)
                     asm volatile("s_nop 1" : "+v"(o0) : : "memory");
@@ -311,10 +292,10 @@ __global__ __launch_bounds__(kThreads, SF_CORRB32_WGS) void corr_build_blocked32
                 }
                 u32x2 o1;
                 o1[0] = __builtin_bit_cast(unsigned, sel1[0]); o1[1] = __builtin_bit_cast(unsigned, sel1[1]);
-                __builtin_amdgcn_raw_buffer_store_b64(o1, rv, SF_VO(vo1), (32 * mt + 2 * jp + 8 * rq) * rec, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(o1, rv, vo1, (32 * mt + 2 * jp + 8 * rq) * rec, 0);
             }
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sel2), rv, SF_VO(vo2), (32 * mt + 8 * rq) * rec, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sel3), rv, SF_VO(vo3), (32 * mt + 8 * rq) * rec, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sel2), rv, vo2, (32 * mt + 8 * rq) * rec, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sel3), rv, vo3, (32 * mt + 8 * rq) * rec, 0);
         }
     }
 }
@@ -332,15 +313,11 @@ __global__ __launch_bounds__(kThreads, SF_CORRB32_WGS) void corr_build_blocked32
 #endif
 constexpr int LP = SF_LOOK32_LP;                // source pixels per workgroup (8 threads each)
 constexpr int kLookThreads = LP * 8;
-#ifndef SF_LOOK32_PASSES
-#define SF_LOOK32_PASSES 1                      // 2: levels 0-1 and 2-3 leave through a half-size transpose buffer (4 workgroups per CU)
-#endif
 constexpr int NCH = 324;
-constexpr int NP = SF_LOOK32_PASSES;
-constexpr int CH_PASS = NCH / NP;               // channels per pass through the transpose buffer
-constexpr int TROW = CH_PASS + 1;               // floats per pixel in the transpose buffer (odd: the read-back of 32 pixels is conflict-free)
+// (two passes -- levels 0-1 and 2-3 through a half-size transpose buffer, 4 workgroups per CU -- were not faster: DESIGN.md 12.9)
+constexpr int TROW = NCH + 1;                   // floats per pixel in the transpose buffer (odd: the read-back of 32 pixels is conflict-free)
 #ifndef SF_LOOK32_PF0
-#define SF_LOOK32_PF0 (SF_LOOK32_PASSES == 1 ? 8 : 5)
+#define SF_LOOK32_PF0 8
 #endif
 constexpr int PF0 = SF_LOOK32_PF0;              // items whose loads are issued up front
 
@@ -355,7 +332,7 @@ struct Look32Args {
 };
 
 template <int AUX>
-__global__ __launch_bounds__(kLookThreads, (NP == 1 ? 768 : 1024) / kLookThreads) void corr_lookup_blocked32_kernel(const Look32Args a) {
+__global__ __launch_bounds__(kLookThreads, 768 / kLookThreads) void corr_lookup_blocked32_kernel(const Look32Args a) {
     __shared__ float T[LP * TROW];
     const int tid = threadIdx.x;
     const int grp = tid >> 4, c = tid & 15;               // 16 lanes per footprint: lane c = footprint column c (10 used)
@@ -377,7 +354,7 @@ __global__ __launch_bounds__(kLookThreads, (NP == 1 ? 768 : 1024) / kLookThreads
         asm volatile("" : "+s"(g_wl[l]), "+s"(g_hl[l]), "+s"(g_nby[l]), "+s"(g_rowb[l]), "+s"(g_off[l]));
     }
     // item it = (level it >> 1, pixel (it & 1) * 16 + grp).  The loads of PF0 items are issued before the first footprint is touched
-    // (one pass: all 32 loads of a thread, 104 VGPRs of data in flight) -- memory-level parallelism is what a gather of cache lines
+    // (all 32 loads of a thread, 104 VGPRs of data in flight) -- memory-level parallelism is what a gather of cache lines
     // that nobody else reads lives on
     struct Item { int ys; float fx, fy; };
     struct Foot { u32x4 w0, w1, w2; unsigned w3; };
@@ -408,13 +385,12 @@ __global__ __launch_bounds__(kLookThreads, (NP == 1 ? 768 : 1024) / kLookThreads
         f[it].w3 = __builtin_amdgcn_raw_buffer_load_b32(rv, ((ys & 3) == 3) ? piece(3) : kDrop, 0, AUX);
     };
     float* o = a.out + (int64_t)img * a.out_img_stride;
-    auto write_out = [&](int ch0) {                        // (channel, pixel): 32 consecutive pixels of a channel = 128 contiguous bytes
+    auto write_out = [&]() {                               // (channel, pixel): 32 consecutive pixels of a channel = 128 contiguous bytes
         __syncthreads();
-        for (int i = tid; i < CH_PASS * LP; i += kLookThreads) {
+        for (int i = tid; i < NCH * LP; i += kLookThreads) {
             const int pix = i % LP, ch = i / LP;
-            if (p0 + pix < a.N) o[(int64_t)(ch0 + ch) * a.N + p0 + pix] = T[pix * TROW + ch];
+            if (p0 + pix < a.N) o[(int64_t)ch * a.N + p0 + pix] = T[pix * TROW + ch];
         }
-        if (ch0 + CH_PASS < NCH) __syncthreads();
     };
 #pragma unroll
     for (int it = 0; it < PF0; ++it) issue(it);
@@ -450,13 +426,12 @@ __global__ __launch_bounds__(kLookThreads, (NP == 1 ? 768 : 1024) / kLookThreads
             R[b] = v * wx0 + dpp_shl1(v) * wx1;
         }
         if (c < 9) {
-            float* t0 = T + pix * TROW + (l * 81 - (NP == 2 && l >= 2 ? CH_PASS : 0)) + c * 9;   // channel l * 81 + a * 9 + b with a = c (corr.py:31-37)
+            float* t0 = T + pix * TROW + l * 81 + c * 9;   // channel l * 81 + a * 9 + b with a = c (corr.py:31-37)
 #pragma unroll
             for (int b = 0; b < 9; ++b) t0[b] = R[b];
         }
-        if (NP == 2 && it == 3) write_out(0);
     }
-    write_out(NCH - CH_PASS);
+    write_out();
 }
 
 }  // namespace

@@ -19,7 +19,6 @@
 // Epilogues as sf_gemm's (bias, GELU, residual, depthwise 1 x 1, AXPY), straight from the accumulator layout: a lane holds 4
 // consecutive rows of one pixel = 8 bytes of a k-octet, or four dwords of four 128-byte row segments.
 #include "weight_ring.h"
-#include <cstdlib>
 
 namespace {
 
@@ -44,9 +43,6 @@ template <int PM> struct StageK { static constexpr int value = (PM == 1) ? 8 : 4
 #ifndef SF_BSTAT_RING
 #define SF_BSTAT_RING 3
 #endif
-#ifndef SF_BSTAT_ALT_ACC
-#define SF_BSTAT_ALT_ACC 0      // (two accumulation chains per tile: measured 0-4 % SLOWER; kept as a switch)
-#endif
 constexpr int RING = SF_BSTAT_RING;    // weight stages in LDS
 #ifndef SF_BSTAT_STORE_SLACK
 #define SF_BSTAT_STORE_SLACK 1
@@ -65,15 +61,7 @@ struct BsArgs {
                           // tile of a grid too small to fill the chip)
     int ntile;            // pixel tiles per image
     int e_ops;            // vector memory operations of one epilogue: stores + the residual loads of the next m-step
-#ifdef SF_BSTAT_TIMERS
-    long long* ts;        // SF_GEMM_TS_BUF: per-wave phase cycle sums (tools/gemm_bs_timers.py; -DSF_BSTAT_TIMERS builds only)
-#endif
 };
-#ifdef SF_BSTAT_TIMERS
-#define SF_BS_STAMP(acc_) { const long long t_ = __builtin_readcyclecounter(); acc_ += t_ - tprev; tprev = t_; }
-#else
-#define SF_BS_STAMP(acc_)
-#endif
 
 // workgroup -> (pixel tile over all images, row range `part` of `nparts`)
 struct WorkItem { int tile, part, nparts; };
@@ -264,22 +252,13 @@ __global__ __launch_bounds__(kThreads, (PM == 1 && NKS <= 16 && RES == 0) ? 4 : 
     const int ms_beg = (int)((int64_t)a.msteps * wi.part / wi.nparts), ms_end = (int)((int64_t)a.msteps * (wi.part + 1) / wi.nparts);
     const int nst = a.nst;
 
-#ifdef SF_BSTAT_TIMERS
-    const long long ts0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
-    long long tw = 0, tb = 0, ti = 0, tm = 0, te = 0, tprev = ts0;
-#endif
     // ---- the wave's activations: B fragments of its 32 pixels for every k-step, loaded once -------------------------------
     f16x8 b[NKS];
     load_b_frags<NKS>(g, z, nc, khalf, nst * SKS, b);
 
     // ---- weights by LDS-DMA: stage (m-step m, stage s) = rows 64 m .. 64 m + 63 x octets 8 s .. 8 s + 7 of each plane -------
-#ifdef SF_BSTAT_REPL      // experiment: SF_BSTAT_REPL copies of the weight planes back to back, workgroups spread over them
-    const int64_t repl_off = (int64_t)((blockIdx.x >> 3) % SF_BSTAT_REPL) * a.a_bytes;
-#else
-    const int64_t repl_off = 0;
-#endif
-    const __amdgpu_buffer_rsrc_t rah = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.A_hi)) + repl_off, 0, a.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ral = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.A_lo)) + repl_off, 0, a.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rah = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.A_hi), 0, a.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ral = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.A_lo), 0, a.a_bytes, 0x00020000);
     auto issue_a = [&](int m, int s, int slot) {
 #pragma unroll
         for (int i = 0; i < kPieces; ++i) {
@@ -462,16 +441,7 @@ __global__ __launch_bounds__(kThreads, (PM == 1 && NKS <= 16 && RES == 0) ? 4 : 
     // everything requested so far has landed (activations, the first two weight stages) and the parameters are visible
     wait_vm<0>();
     __syncthreads();
-#ifdef SF_BSTAT_TIMERS
-    const long long ts1 = __builtin_readcyclecounter();
-    tprev = ts1;
-#endif
 
-#ifdef SF_BSTAT_STAGGER
-    // experiment: the second workgroup of a CU (dispatch order: 32 CUs per XCD are filled once before any gets its second
-    // workgroup) starts its weight loop half an m-step late, so that its epilogues fall into the other one's MFMA stages
-    if ((blockIdx.x >> 8) & 1) __builtin_amdgcn_s_sleep(SF_BSTAT_STAGGER);
-#endif
     int slot = 0;
     const char* sa_base = smem + (khalf * 64 + l31) * 16;
     for (int m = ms_beg; m < ms_end; ++m) {
@@ -491,15 +461,11 @@ __global__ __launch_bounds__(kThreads, (PM == 1 && NKS <= 16 && RES == 0) ? 4 : 
             if (s < nst) {                                                                // (wave-uniform)
                 // this wave's pieces of the stage have landed: behind them in the queue are the pieces of the next stage and,
                 // in the first two stages of an m-step, the previous epilogue's stores / this m-step's residual loads
-                SF_BS_STAMP(tm)
                 if (s < RING - 1) wait_vm_epi<kPieces * (RING - 2)>(a.e_ops);
                 else wait_vm<kPieces * (RING - 2)>();
-                SF_BS_STAMP(tw)
                 __builtin_amdgcn_s_barrier();                      // ... everyone's; and nobody reads the previous slot any more
-                SF_BS_STAMP(tb)
                 issue_a(ma, sa, slot == 0 ? RING - 1 : slot - 1);  // RING - 1 stages ahead, into the slot just released
                 advance();
-                SF_BS_STAMP(ti)
                 __builtin_amdgcn_sched_barrier(0);
                 const char* sp = sa_base + slot * kStage;
                 // the stage's MFMAs: fragment f = (k-step, product, tile) is read once and used by ONE MFMA
@@ -534,22 +500,13 @@ __global__ __launch_bounds__(kThreads, (PM == 1 && NKS <= 16 && RES == 0) ? 4 : 
                 slot = (slot == RING - 1) ? 0 : slot + 1;
             }
         }
-        SF_BS_STAMP(tm)
         run_epilogue(m);
-        SF_BS_STAMP(te)
     }
     wait_vm<0>();                                                  // (pieces requested past the end must land before the LDS is released)
-#ifdef SF_BSTAT_TIMERS
-    if (a.ts && lane == 0 && blockIdx.x < 4096) {
-        long long* d = a.ts + ((int64_t)blockIdx.x * 4 + wave) * 8;
-        d[0] = ts1 - ts0; d[1] = tw; d[2] = tb; d[3] = ti; d[4] = tm; d[5] = te; d[6] = __builtin_readcyclecounter() - ts0;
-        d[7] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
-#endif
 }
 
 // ---- software-pipelined form for the GELU -> k-octet layers (ffn*.0, pw, fc1: 60 % of the family's time) ----------------------
-// The phase timers of the kernel above (tools/gemm_bs_timers.py, M960 K640, one product) put 31 % of a wave's life into its
+// The phase timers of the kernel above (round 5, recorded under profiles/; M960 K640, one product) put 31 % of a wave's life into its
 // epilogues (3300 of 9400 cycles per 64 rows: GELU is ~18 VALU instructions per pair of values), during which the wave
 // issues no MFMA; with only two waves per SIMD (K = 640 costs 160 registers) nothing else fills the matrix pipe.  Here the
 // wave pipelines itself: it walks the rows in tiles of 32 with TWO accumulators, and the epilogue of tile i is cut into
@@ -575,10 +532,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bstat_gk_kernel(const BsArgs
     const int NT = (g.M + 31) / 32;                                                       // row tiles
     const int t_beg = (int)((int64_t)NT * wi.part / wi.nparts), t_end = (int)((int64_t)NT * (wi.part + 1) / wi.nparts);
 
-#ifdef SF_BSTAT_TIMERS
-    const long long ts0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
-    long long tw = 0, tb = 0, ti = 0, tm = 0, te = 0, tprev = ts0;
-#endif
     f16x8 b[NKS];
     load_b_frags<NKS>(g, z, nc, khalf, NKS, b);
 
@@ -653,10 +606,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bstat_gk_kernel(const BsArgs
 
     wait_vm<0>();
     __syncthreads();
-#ifdef SF_BSTAT_TIMERS
-    const long long ts1 = __builtin_readcyclecounter();
-    tprev = ts1;
-#endif
 
     int slot = 0;
     const char* sp_base = smem + lane * 16;
@@ -672,17 +621,10 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bstat_gk_kernel(const BsArgs
 #pragma unroll
             for (int e = 0; e < 4; ++e) cur[4 * j + e] = b4[e];
         }
-#if SF_BSTAT_ALT_ACC
-        // Two accumulation chains per tile (fragments alternate between `cur` and `alt`, summed at the end of the tile): an MFMA that
-        // depends on the one before it AND has other instructions issued in between (here: a fragment read and a share of the previous
-        // tile's epilogue behind every MFMA) waits for that MFMA's write-back -- ~40 cycles on top of the 32 it occupies the pipe
-        // (MI355X_MICROARCH.md, "one EXTRA issue slot between two MFMAs on the SAME accumulator"); with two chains the neighbour is
-        // independent.  With two products `cur` collects the lo products and `alt` the hi ones.
-        f32x16 alt = {};
-#endif
+        // (two accumulation chains per tile, fragments alternating between them and summed at the end, measured 0-4 % SLOWER:
+        // DESIGN.md 12.9)
         static_for<0, NS>([&](auto s_tag) {
             constexpr int s = decltype(s_tag)::value;
-            SF_BS_STAMP(tm)
             // this wave's pieces of the stage have landed.  Younger than them in the in-order queue: the refill issued at the end of the
             // previous stage (P pieces) AND the epilogue stores of the previous stage (one 8-byte store per group) -- counting those too
             // leaves them in flight for a whole stage instead of draining them here (SF_BSTAT_STORE_SLACK)
@@ -693,19 +635,12 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bstat_gk_kernel(const BsArgs
                 constexpr int kSt = (SF_BSTAT_STORE_SLACK && had) ? kB + (sp < kR ? 1 : 0) : 0;
                 wait_vm<P * (RING - 2) + kSt>();
             }
-            SF_BS_STAMP(tw)
             __builtin_amdgcn_s_barrier();                          // ... everyone's; nobody reads the previous slot any more
-            SF_BS_STAMP(tb)
             __builtin_amdgcn_sched_barrier(0);
-            SF_BS_STAMP(ti)
             const char* sp = sp_base + slot * kStage;
 #pragma unroll
             for (int i = 0; i < S; ++i) {
                 const f16x8 fr = *reinterpret_cast<const f16x8*>(sp + i * 1024);
-#if SF_BSTAT_ALT_ACC
-                if ((s * S + i) & 1) alt = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr, b[(s * S + i) / PM], alt, 0, 0, 0);
-                else
-#endif
                 cur = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr, b[(s * S + i) / PM], cur, 0, 0, 0);
             }
             // groups of the previous tile's epilogue that belong to this stage: 4 groups spread over the NS stages
@@ -741,10 +676,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bstat_gk_kernel(const BsArgs
             __builtin_amdgcn_sched_barrier(0);
             slot = (slot == RING - 1) ? 0 : slot + 1;
         });
-#if SF_BSTAT_ALT_ACC
-#pragma unroll
-        for (int e = 0; e < 16; ++e) cur[e] += alt[e];
-#endif
     };
 
     using std::integral_constant;
@@ -773,15 +704,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_bstat_gk_kernel(const BsArgs
             epi_groups(acc0, tau - 1, integral_constant<int, 2>{}, integral_constant<int, 2>{});
         }
     }
-    SF_BS_STAMP(tm)
     wait_vm<0>();                                                  // (pieces requested past the end must land before the LDS is released)
-#ifdef SF_BSTAT_TIMERS
-    if (a.ts && lane == 0 && blockIdx.x < 4096) {
-        long long* d = a.ts + ((int64_t)blockIdx.x * 4 + wave) * 8;
-        d[0] = ts1 - ts0; d[1] = tw; d[2] = tb; d[3] = ti; d[4] = tm; d[5] = rt0;   /* (gk: start time, 100 MHz) */ d[6] = __builtin_readcyclecounter() - ts0;
-        d[7] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
-#endif
 }
 
 template <int PM>
@@ -925,15 +848,9 @@ int gemm_bstat_launch(const SfGemm& g, hipStream_t st) {
         if (g.c_f16 == 3 && (g.M & 3)) a.e_ops = 0;
     }
     const int64_t grid_x = n_main + (wgs - n_main) * f;
-#ifdef SF_BSTAT_TIMERS
-    a.ts = getenv("SF_GEMM_TS_BUF") ? (long long*)strtoull(getenv("SF_GEMM_TS_BUF"), nullptr, 0) : nullptr;
-#endif
     dim3 grid((unsigned)grid_x);
-#ifndef SF_BSTAT_PIPELINED
-#define SF_BSTAT_PIPELINED 1
-#endif
     // GELU -> k-octets (the FFN hiddens, x4, the temporal MLP hidden): the software-pipelined kernel
-    if (SF_BSTAT_PIPELINED && g.epilogue == SF_EPI_GELU && g.c_f16 == 2) {
+    if (g.epilogue == SF_EPI_GELU && g.c_f16 == 2) {
         return (g.precision == SF_PRECISION_F16) ? launch_gk<1>(a, grid, st) : launch_gk<2>(a, grid, st);
     }
     return (g.precision == SF_PRECISION_F16) ? launch_nks<1>(a, grid, st) : launch_nks<2>(a, grid, st);

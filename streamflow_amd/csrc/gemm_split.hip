@@ -29,7 +29,6 @@
 #include "sf_common.h"
 #include "gemm_epilogue.h"
 #include "split_operand.h"
-#include <cstdlib>
 
 namespace {
 
@@ -41,18 +40,8 @@ using namespace sf_split;
 struct SplitArgs {
     SfGemm g;
     int64_t a_bytes, b_bytes;      // bytes spanned by one batch image of A / B (buffer range check)
-#ifdef SF_GEMM_TIMERS
-    long long* ts;                 // SF_GEMM_TS_BUF: per-workgroup phase timestamps (tools/gemm_one.py; built with
-                                   // tools/build_variant.sh timers gemm_split.hip -DSF_GEMM_TIMERS)
-#endif
 };
 
-#ifndef SF_GEMM_FAST_GELU
-#define SF_GEMM_FAST_GELU 1      // A/B knob: 0 = the rational erf GELU in every mode
-#endif
-#ifndef SF_GEMM_FRAG_PREFETCH
-#define SF_GEMM_FRAG_PREFETCH 0
-#endif
 #ifndef SF_GEMM_WAVES
 #define SF_GEMM_WAVES 3          // workgroups per CU the register budget is sized for (128x128 tile)
 #endif
@@ -70,17 +59,15 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
     constexpr bool kDmaA = (ALAY == 2) && (BM == 128);
     constexpr int kAStage = (SA ? 2 : 1) * (BK / 8) * BM * 8;                    // halfs of one DMA stage (hi [+ lo])
     constexpr int kAHalfs = kDmaA ? 2 * kAStage : (SA ? 2 : 1) * BM * LDK;
-#ifndef SF_GEMM_B2
-#define SF_GEMM_B2 1     // two B stages where they fit (no lo plane + DMA-fed A): ONE barrier per k-tile instead of two
-#endif
-    // kB2: B double-buffered in LDS.  The staged registers of tile kt+1 are written to the OTHER stage right after the
+    // kB2: two B stages where they fit (no lo plane + DMA-fed A): ONE barrier per k-tile instead of two (+0.3 % on the GEMM
+    // family against one stage, docs/DESIGN_log_r1_r3.md).  The staged registers of tile kt+1 are written to the OTHER stage right after the
     // MFMAs of tile kt (nobody reads that stage: it was last read in tile kt-1, a barrier ago), so the barrier that
     // separated "everyone is done reading" from the store disappears.
     // kDmaB: B arrives as fp16 k-octet planes (SF_LAYOUT_F16_KOCT) and is DMA-fed like A: two stages [4 k-octets][BN][8]
     constexpr bool kDmaB = (BLAY == SF_LAYOUT_F16_KOCT);
     static_assert(!kDmaB || (kDmaA && !SB), "k-octet B needs the DMA-fed 128-row tile and has no lo plane");
     constexpr int kBStage = (BK / 8) * BN * 8;                                   // halfs of one DMA stage of B
-    constexpr bool kB2 = SF_GEMM_B2 && !SB && kDmaA && !kDmaB;
+    constexpr bool kB2 = !SB && kDmaA && !kDmaB;
     constexpr int kMainHalfs = kAHalfs + (kDmaB ? 2 * kBStage : (SB ? 2 : (kB2 ? 2 : 1)) * BN * LDK);   // SB = false: no lo part
     constexpr int kEpiHalfs = 4 * sf::kEpiScratchFloats * 2;
     __shared__ __attribute__((aligned(1024))) _Float16 smem[kMainHalfs > kEpiHalfs ? kMainHalfs : kEpiHalfs];
@@ -94,10 +81,6 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
     const int ksp = g.k_splits > 1 ? g.k_splits : 1;
     const int n0 = tc.n_tile * BN, m0 = tc.m_tile * BM, z = tc.z / ksp, split = tc.z % ksp;
 
-#ifdef SF_GEMM_TIMERS
-    const long long ts0 = __builtin_readcyclecounter();
-    const long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
     typedef typename OperandSel<BN, BLAY>::type OperandB;
     Operand<BM, ALAY> opa;
     OperandB opb;
@@ -178,9 +161,6 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
     opb.template store<SB>(kt_beg * BK, sB[0], sB[SB ? 1 : 0], rb, conv ? conv_tap(kt_beg * BK) : -1);
     if (kDmaA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#ifdef SF_GEMM_TIMERS
-    const long long ts1 = __builtin_readcyclecounter();
-#endif
 
     const int khalf = lane >> 5, l31 = lane & 31;
     for (int kt = kt_beg; kt < kt_end; ++kt) {
@@ -191,10 +171,8 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
             if (kDmaA) issue_a(kt + 1, abuf ^ 1);          // the other stage was last read one k-tile (two barriers) ago
             else opa.load((kt + 1) * BK, ca.off, ra);
             if (kDmaB) issue_b(kt + 1, abuf ^ 1);
-#ifndef SF_ABLATE_B          // timing ablation only (wrong results): B tile staged once, never refreshed
             if (conv) opb.load((kt + 1) * BK, conv_off((kt + 1) * BK), rb, conv_shift((kt + 1) * BK), conv_tap((kt + 1) * BK));
             else opb.load((kt + 1) * BK, cb.off, rb);
-#endif
         }
         // keep the staged loads in flight across the MFMA block: nothing below may be hoisted above it
         __builtin_amdgcn_sched_barrier(0);
@@ -210,46 +188,8 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
         const _Float16* pbh = kDmaB ? smem + kAHalfs + abuf * kBStage + (khalf * BN + wn * TN * 32 + l31) * 8
                                     : sB[bbuf] + (wn * TN * 32 + l31) * LDK + khalf * 8;
         const _Float16* pbl = sB[SB ? 1 : 0] + (wn * TN * 32 + l31) * LDK + khalf * 8;
-#if SF_GEMM_FRAG_PREFETCH
-        // all fragment reads of the k-tile are issued before its first MFMA (2 k-steps x 8 x ds_read_b128 = 64 VGPRs):
-        // the LDS latency is exposed once per k-tile instead of once per register reuse (hipcc otherwise recycles 24
-        // fragment registers and waits lgkmcnt(0) three times per k-step)
-        f16x8 ah[BK / 16][TM], al[BK / 16][TM], bh[BK / 16][TN], bl[BK / 16][TN];
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                ah[ks][i] = *reinterpret_cast<const f16x8*>(pah + i * kATile + ks * kAStep);
-                if (SA) al[ks][i] = *reinterpret_cast<const f16x8*>(pal + i * kATile + ks * kAStep);
-            }
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                bh[ks][j] = *reinterpret_cast<const f16x8*>(pbh + j * kBTile + ks * kBStep);
-                if (SB) bl[ks][j] = *reinterpret_cast<const f16x8*>(pbl + j * kBTile + ks * kBStep);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-            // product-major order: the three MFMAs that hit one accumulator are TM*TN instructions apart
-            if (SA) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ks][i], bh[ks][j], acc[i][j], 0, 0, 0);
-            }
-            if (SB) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks][i], bl[ks][j], acc[i][j], 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks][i], bh[ks][j], acc[i][j], 0, 0, 0);
-        }
-#else
+        // (issuing all 16 fragment reads of the k-tile before its first MFMA -- 163 VGPRs -- measured -3 % on the step in f16x3
+        // and neutral in f16x2: docs/DESIGN_log_r1_r3.md)
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
             f16x8 ah[TM], al[TM], bh[TN], bl[TN];
@@ -273,24 +213,19 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
                 }
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if (kt + 1 < kt_end) {
             if (!kB2 && !kDmaB) __syncthreads();   // every wave is done reading tile kt
             if (!kDmaA) opa.template store<SA>((kt + 1) * BK, sA[0], sA[SA ? 1 : 0], ra);
-#ifndef SF_ABLATE_B
             opb.template store<SB>((kt + 1) * BK, sB[kB2 ? (bbuf ^ 1) : 0], sB[SB ? 1 : 0], rb, conv ? conv_tap((kt + 1) * BK) : -1);
-#endif
             if (kDmaA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (already retired by the wait for rb)
             __syncthreads();
         }
     }
-#ifdef SF_GEMM_TIMERS
-    const long long ts2 = __builtin_readcyclecounter();
-#endif
     // the two-product modes evaluate GELU as a polynomial (sf_common.h) WHERE THE RESULT LEAVES AS fp16 (the k-octet
     // epilogue): a tenth of the rounding it receives there; results kept in fp32 use the erf-rational form in every mode
-    constexpr bool kFastGelu = (PM <= 2) && SF_GEMM_FAST_GELU;
+    // (240.9 -> 243.9 ff/s at an unchanged EPE; the polynomial everywhere cost 1e-4 px: docs/DESIGN_log_r1_r3.md)
+    constexpr bool kFastGelu = (PM <= 2);
     SfGemm gs = g;
     if (ksp > 1) gs.C = g.C + (int64_t)split * g.split_stride;   // partial product of this K slice: its own slab
     if (gs.c_f16 == 2) {
@@ -304,20 +239,12 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
     } else {
         gemm_epilogue<WM, WN, TM, TN>(gs, acc, m0, n0, z, wm, wn, lane);
     }
-#ifdef SF_GEMM_TIMERS
-    if (args.ts && tid == 0) {
-        long long* d = args.ts + (int64_t)blockIdx.x * 8;
-        d[0] = ts0; d[1] = ts1; d[2] = ts2; d[3] = __builtin_readcyclecounter();
-        d[4] = rt0; d[5] = __builtin_amdgcn_s_memrealtime();
-        d[6] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));      // XCC_ID[3:0]
-        d[7] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));      // HW_ID
-    }
-#endif
 }
 
 
 // ---- "B-direct" kernel: split weights x fp16 k-octet activations (SF_LAYOUT_SPLIT_F16 x SF_LAYOUT_F16_KOCT) ----------------
-// 128 (rows) x 256 (pixels) tile, 8 waves as 2 (rows) x 4 (pixels), each 64 x 64 = 2 x 2 MFMA tiles.
+// 128 (rows) x 256 (pixels) tile, 8 waves side by side, each all 128 rows x 32 pixels = 4 x 1 MFMA tiles: every activation
+// fragment is loaded once and feeds four MFMAs; every wave reads all weight fragments from LDS.
 //  * WEIGHTS (shared by all waves) go L2 -> LDS by DMA into a ring of three 32-deep stages: ONE 1-KB piece per plane
 //    (hi, lo) per wave and stage, requested two stages ahead, waited for with a counted vmcnt;
 //  * ACTIVATIONS are private to a wave column, and in the k-octet planes a lane's MFMA B fragment (8 consecutive k of one
@@ -329,17 +256,13 @@ __global__ __launch_bounds__(kThreads, (TM * TN >= 8) ? 2 : SF_GEMM_WAVES) void 
 // 16 MFMAs of EIGHT waves, and 16 waves per CU (128 registers) instead of 12.
 // Same epilogues (gemm_epilogue.h) as the 128 x 128 kernel.
 constexpr int kBdThreads = 512;
-// wave grid WM x (8 / WM): 2 x 4 (64 x 64 per wave: every activation fragment is loaded by two waves) or 1 x 8 (each wave all
-// 128 rows x 32 pixels: no duplicate activation loads, but every wave re-reads all weight fragments from LDS)
-// BM = 256 (single-product weights only: three 16-KB stages): 2 x 4 waves of 128 x 64 -- every activation fragment feeds FOUR
-// MFMAs of a wave instead of two and is pulled from L2 once per 256 output rows instead of once per 128: the activations
-// (N = images x pixels columns) are the large operand of every GEMM of the update block, the weights are not.
-template <int PM, int WM, int BM>
+// (A 2 x 4 wave grid of 64 x 64 measured equal within the noise for two-product layers and slower for single-product ones
+// (DESIGN.md section 11), and at its 128-register cap its epilogue spilled 140 VGPRs; a 256-row tile of
+// 2 x 4 waves for single-product weights was no better than this one either.  Both were removed.)
+template <int PM>
 __device__ __forceinline__ void gemm_bdirect_body(const SplitArgs& args) {
     const SfGemm& g = args.g;
-    static_assert(BM == 128 || (BM == 256 && PM == 1 && WM == 2), "the 256-row tile is built for one product, 2 x 4 waves");
-    constexpr int BN = 256, WN = 8 / WM, TM = BM / 32 / WM, TN = WM, NST = 3;
-    constexpr int NPC = BM / 128;                                    // DMA pieces per wave, plane and stage
+    constexpr int BM = 128, BN = 256, WM = 1, WN = 8, TM = 4, TN = 1, NST = 3;
     constexpr int kPlane = (BK / 8) * BM * 16;                       // bytes of one plane (hi or lo) of a stage: 8 KB
     constexpr int kStage = PM * kPlane;
     constexpr int kEpiBytes = 8 * sf::kEpiScratchFloats * 4;
@@ -358,23 +281,15 @@ __device__ __forceinline__ void gemm_bdirect_body(const SplitArgs& args) {
     const int a_plane = (int)(args.a_bytes);
     const __amdgpu_buffer_rsrc_t rah = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.A_hi), 0, a_plane, 0x00020000);
     const __amdgpu_buffer_rsrc_t ral = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g.A_lo), 0, a_plane, 0x00020000);
-    int voa[NPC];
-#pragma unroll
-    for (int p_ = 0; p_ < NPC; ++p_) {
-        const int sl = tid + p_ * kBdThreads;                        // slot = k-octet * BM + row
-        voa[p_] = ((sl / BM) * (int)g.lda_h + m0 + (sl % BM)) * 16;
-    }
+    const int voa = ((tid / BM) * (int)g.lda_h + m0 + (tid % BM)) * 16;
     auto issue_a = [&](int kt, int slot) {
         const int so = kt * (BK / 8) * (int)g.lda_h * 16;
-#pragma unroll
-        for (int p_ = 0; p_ < NPC; ++p_) {
-            char* dst = smem + slot * kStage + (p_ * 8 + wave) * 1024;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rah, (lds_ptr)(dst), 16, voa[p_], so, 0, 0);
-            if (PM == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(ral, (lds_ptr)(dst + kPlane), 16, voa[p_], so, 0, 0);
-        }
+        char* dst = smem + slot * kStage + wave * 1024;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rah, (lds_ptr)(dst), 16, voa, so, 0, 0);
+        if (PM == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(ral, (lds_ptr)(dst + kPlane), 16, voa, so, 0, 0);
     };
     // ---- activations straight into registers: fragment (j, k-step ks) of stage kt = k-octet 4 kt + 2 ks + khalf of pixel
-    // n0 + (wn * 2 + j) * 32 + l31 (pixels past N clamped: never stored) ----
+    // n0 + (wn * TN + j) * 32 + l31 (pixels past N clamped: never stored) ----
     const __amdgpu_buffer_rsrc_t rbd = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char*>(reinterpret_cast<const char*>(g.B)) + (int64_t)z * g.strideB * 2, 0, (int)args.b_bytes, 0x00020000);
     int vob[TN];
@@ -408,27 +323,16 @@ __device__ __forceinline__ void gemm_bdirect_body(const SplitArgs& args) {
     issue_a(1, 1);
     const int offa = (khalf * BM + wm * TM * 32 + l31) * 16;
     int slot = 0, slot2 = 2;
-#ifdef SF_GEMM_TIMERS
-    const long long ts0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
-    long long tw = 0, tb = 0, ti = 0, tm = 0, tprev = ts0;
-#define SF_BD_STAMP(acc_) { const long long t_ = __builtin_readcyclecounter(); acc_ += t_ - tprev; tprev = t_; }
-#else
-#define SF_BD_STAMP(acc_)
-#endif
     auto stage = [&](int kt, u32x4 (&bcur)[BK / 16][TN], u32x4 (&bnext)[BK / 16][TN]) {
-        SF_BD_STAMP(tm)
         // stage kt of the weights has landed (this wave's pieces; the barrier makes it everyone's): behind it in the queue
         // are only B(kt) -- needed now anyway -- and the PM pieces of DMA(kt + 1)
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (PM * NPC));                             // vmcnt(PM * NPC)
-        SF_BD_STAMP(tw)
+        __builtin_amdgcn_s_waitcnt(0x0F70 | PM);                                     // vmcnt(PM)
         __builtin_amdgcn_s_barrier();                       // ... and slot2 (stage kt - 1) is no longer read by anyone
-        SF_BD_STAMP(tb)
         // (unconditional, also past the last stage -- out-of-range buffer reads return zeros into registers / a slot nobody
         // reads: with the same number of memory operations behind every load on every path, hipcc's vmcnt waits are exact;
         // with `if (kt + 1 < nk)` around them it sizes them for the shortest path, i.e. vmcnt(1) and (0))
         load_b(kt + 1, bnext);
         issue_a(kt + 2, slot2);
-        SF_BD_STAMP(ti)
         const char* sa = smem + slot * kStage + offa;
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
@@ -454,43 +358,19 @@ __device__ __forceinline__ void gemm_bdirect_body(const SplitArgs& args) {
         stage(kt, bq0, bq1);
         stage(kt + 1, bq1, bq0);
     }
-    constexpr bool kFastGelu = SF_GEMM_FAST_GELU;
     // the stages issue DMA pieces past the end of K unconditionally (zero fills): drain them explicitly before the stage ring
     // becomes the epilogues' transpose scratch -- a late piece would otherwise land in another wave's scratch
     __builtin_amdgcn_s_waitcnt(0x0070);                      // vmcnt(0) lgkmcnt(0)
     __syncthreads();
-#ifdef SF_GEMM_TIMERS
-    const long long ts2 = __builtin_readcyclecounter();
-#endif
     float* scratch = reinterpret_cast<float*>(smem) + wave * sf::kEpiScratchFloats;
-    if (g.c_f16 == 2) sf::gemm_epilogue_koct<WM, WN, TM, TN, kFastGelu>(g, acc, m0, n0, z, wm, wn, lane, scratch);
+    if (g.c_f16 == 2) sf::gemm_epilogue_koct<WM, WN, TM, TN, true>(g, acc, m0, n0, z, wm, wn, lane, scratch);
     else if (sf::epilogue_vec_ok(g, z)) sf::gemm_epilogue_vec<WM, WN, TM, TN>(g, acc, m0, n0, z, wm, wn, lane, scratch);
     else gemm_epilogue<WM, WN, TM, TN>(g, acc, m0, n0, z, wm, wn, lane);
-#ifdef SF_GEMM_TIMERS
-    if (args.ts && lane == 0 && blockIdx.x < 8192) {
-        long long* d = args.ts + ((int64_t)blockIdx.x * 8 + wave) * 8;
-        d[0] = ts0; d[1] = tw; d[2] = tb; d[3] = ti; d[4] = tm; d[5] = ts2 - ts0; d[6] = __builtin_readcyclecounter() - ts2;
-        d[7] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
-#endif
 }
-// (two __global__ wrappers: a __launch_bounds__ that depends on a template parameter left hipcc without the host stub of
-// some instantiations -- "undefined symbol __device_stub__gemm_bdirect_kernel<1, 2, 256>" at load time)
-// Wave grid: 1 x 8 waves of 128 x 32 (every activation fragment loaded once, used for four MFMAs) is what ships.  The 2 x 4
-// grid of 64 x 64 measured equal within the noise for two-product layers and slower for single-product ones (DESIGN.md
-// section 11), and at its 128-register cap its epilogue spilled 140 VGPRs; the 256-row tile was no better
-// than 1 x 8 either.  Both stay reachable for experiments: tools/build_variant.sh ... -DSF_GEMM_BD_WM=2 / -DSF_GEMM_BD256_MIN_M=..
-#ifndef SF_GEMM_BD_WM
-#define SF_GEMM_BD_WM 1
-#endif
-#ifndef SF_GEMM_BD256_MIN_M
-#define SF_GEMM_BD256_MIN_M 0            // 0 = never
-#endif
+// (a __global__ wrapper around the body: written as the kernel itself the same source compiles to other code -- two VGPRs fewer,
+// 14 more s_waitcnt; profiles/retire_kernel_switches.md)
 template <int PM>
-__global__ __launch_bounds__(kBdThreads, 4) void gemm_bdirect_kernel(const SplitArgs args) { gemm_bdirect_body<PM, SF_GEMM_BD_WM, 128>(args); }
-#if SF_GEMM_BD256_MIN_M
-__global__ __launch_bounds__(kBdThreads, 2) void gemm_bdirect256_kernel(const SplitArgs args) { gemm_bdirect_body<1, 2, 256>(args); }
-#endif
+__global__ __launch_bounds__(kBdThreads, 4) void gemm_bdirect_kernel(const SplitArgs args) { gemm_bdirect_body<PM>(args); }
 
 template <int WM, int WN, int TM, int TN, int PM>
 int launch_cfg(const SplitArgs& a, hipStream_t st) {
@@ -511,13 +391,10 @@ int launch_cfg(const SplitArgs& a, hipStream_t st) {
         if constexpr (!SB && WM * TM * 32 == 128) {
             // B-direct kernel (128 x 256 tile, activations straight into registers).  Dispatch rule, measured per shape
             // (tools/gemm_koct_bench.py, 24 x 7040 pixels) and fixed at compile time (experiments:
-            // tools/build_variant.sh with -DSF_GEMM_BD_MIN_M / -DSF_GEMM_BD_MIN_WG / -DSF_GEMM_BDIRECT=0):
+            // tools/build_variant.sh with -DSF_GEMM_BD_MIN_M / -DSF_GEMM_BD_MIN_WG):
             //  * M >= 192 (+0..15 %), or one row tile (96 < M <= 128) with a short K <= 192 (M128 K192 33.1 -> 29.7 us; K = 960: no);
             //  * only when the 128 x 256 tiles fill the chip: a single clip gives M = 384 just 249 of them for 256 CUs and runs
             //    better on the 128 x 128 kernel (threshold 0: 186.7 / 189.2 ff/s, 384: 192.7 / 192.6); batched steps always pass.
-#ifndef SF_GEMM_BDIRECT
-#define SF_GEMM_BDIRECT 1
-#endif
 #ifndef SF_GEMM_BD_MIN_M
 #define SF_GEMM_BD_MIN_M 192
 #endif
@@ -526,16 +403,9 @@ int launch_cfg(const SplitArgs& a, hipStream_t st) {
 #endif
             const int64_t n_wg2 = (int64_t)sf::ceil_div(g.N, 256) * sf::ceil_div(g.M, 128) * g.batch;
             const bool bd_m = g.M >= SF_GEMM_BD_MIN_M || (g.M > 96 && g.K <= 192);
-            if (SF_GEMM_BDIRECT && bd_m && n_wg2 >= SF_GEMM_BD_MIN_WG && g.k_splits <= 1 && (int64_t)g.ldb * 16 * 2 < ((int64_t)1 << 31)) {
+            if (bd_m && n_wg2 >= SF_GEMM_BD_MIN_WG && g.k_splits <= 1 && (int64_t)g.ldb * 16 * 2 < ((int64_t)1 << 31)) {
                 dim3 grid2(sf::ceil_div(g.N, 256) * sf::ceil_div(g.M, 128) * g.batch);
                 if (sf::gemm_route_probe()) return sf::gemm_route_report(SF_GEMM_FAMILY_BDIRECT, BM, PM);
-#if SF_GEMM_BD256_MIN_M
-                if (PM == 1 && sf::ceil_div(g.M, 256) * 256 == sf::ceil_div(g.M, 128) * 128 && g.M >= SF_GEMM_BD256_MIN_M) {
-                    dim3 grid3(sf::ceil_div(g.N, 256) * sf::ceil_div(g.M, 256) * g.batch);
-                    hipLaunchKernelGGL(gemm_bdirect256_kernel, grid3, dim3(kBdThreads), 0, st, a);
-                    return sf::check_launch("sf_gemm(B-direct 256)");
-                }
-#endif
                 hipLaunchKernelGGL((gemm_bdirect_kernel<PM>), grid2, dim3(kBdThreads), 0, st, a);
                 return sf::check_launch("sf_gemm(B-direct)");
             }
@@ -574,11 +444,6 @@ int pick_tile(const SplitArgs& a, hipStream_t st) {
     // waste more than a quarter of the MFMAs
     const int M = g.M;
     auto padded = [&](int bm) { return (M + bm - 1) / bm * bm; };
-#ifdef SF_GEMM_BM                                        // experiment builds only (tools/build_variant.sh ... -DSF_GEMM_BM=64)
-    if (SF_GEMM_BM == 128) return launch_cfg<2, 2, 2, 2, PM>(a, st);
-    if (SF_GEMM_BM == 64) return launch_cfg<1, 4, 2, 1, PM>(a, st);
-    if (SF_GEMM_BM == 32) return launch_cfg<1, 4, 1, 1, PM>(a, st);
-#endif
     // (a wave-specialised producer/consumer variant of the 128x128 kernel was faster for K >= 768 early in the round;
     // after the cheaper split and epilogue it measured 2-25 % slower at every batch size and was removed)
     if (padded(128) * 4 <= M * 5) return launch_cfg<2, 2, 2, 2, PM>(a, st);
@@ -742,9 +607,6 @@ int gemm_split_dispatch_inner(const SfGemm& g, hipStream_t st) {
     if (g.b_group % 32) return fail(SF_ERR_BAD_ARG, "sf_gemm(f16x3): b_group must be a multiple of 32");
     SplitArgs a;
     a.g = g;
-#ifdef SF_GEMM_TIMERS
-    a.ts = getenv("SF_GEMM_TS_BUF") ? (long long*)strtoull(getenv("SF_GEMM_TS_BUF"), nullptr, 0) : nullptr;
-#endif
     if (g.a_layout == SF_LAYOUT_SPLIT_F16) {
         if (!g.A_hi || !g.A_lo || g.lda_h < (g.M + 127) / 128 * 128 || (g.lda_h & 127) ||
             ((reinterpret_cast<uintptr_t>(g.A_hi) | reinterpret_cast<uintptr_t>(g.A_lo)) & 15))

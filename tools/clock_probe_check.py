@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Does sf_clock_probe run BESIDE the load, and what does it read?  (a) probe alone; (b) probe beside a loop of the two-product K = 640
-GEMM; (c) the GEMM's own in-kernel clock needs the timers build (tools/gemm_bs_timers.py).  Prints wall times so that serialisation
+GEMM; (c) the GEMM's own in-kernel clock would need cycle counters in the kernel, which no build has any more.  Prints wall times so that serialisation
 (probe first, load after) would show."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Correlation-volume build alone at the Sintel shape (timing / rocprofv3 runs).  argv: reps [h w]
-SF_CLIPS=8 sets the clips, SF_CORR_DTYPE=f16|f32 the volume format; SF_CORR_TS=1 prints per-workgroup phase timers of
-the fp16 build (needs tools/build_variant.sh timers corr.hip -DSF_CORR_TIMERS and SF_HIP_LIB=.../variant_timers.so)."""
+SF_CLIPS=8 sets the clips, SF_CORR_DTYPE=f16|f32 the volume format."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,20 +22,6 @@ def run():
 for _ in range(3):
     run()
 torch.cuda.synchronize()
-if os.environ.get("SF_CORR_TS"):
-    ts = torch.zeros(65536 * 8, dtype=torch.int64, device=dev)
-    os.environ["SF_CORR_TS_BUF"] = str(ts.data_ptr())
-    run(); torch.cuda.synchronize()
-    os.environ.pop("SF_CORR_TS_BUF")
-    t = ts.view(-1, 8).cpu().double()
-    t = t[t[:, 0] > 0]
-    print("workgroups", t.shape[0])
-    for name, v in (("k-loop", t[:, 1] - t[:, 0]), ("epilogue", t[:, 2] - t[:, 1])):
-        print(f"{name:9s} mean {v.mean().item():9.0f} median {v.median().item():9.0f} min {v.min().item():9.0f} max {v.max().item():9.0f} cycles")
-    dt_c, dt_r = t[:, 2] - t[:, 0], t[:, 4] - t[:, 3]
-    print(f"clock: {(dt_c.sum() / dt_r.sum()).item() * 100:.0f} MHz")
-    span = (t[:, 4].max() - t[:, 3].min()).item() / 100.0
-    print(f"kernel span {span:.1f} us; resident workgroups on average {dt_r.sum().item() / 100.0 / span:.1f} (max 768)")
 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 s.record()
 for _ in range(reps):

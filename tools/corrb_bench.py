@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Correlation build + lookup, row-major fp16 volumes vs blocked fp16 volumes, at a BASELINE shape.
-argv: workload (sintel|kitti|spring) [clips] [reps].  Prints one JSON line per variant (us, algorithmic GB/s by SURVEY 8d).
-SF_CORR_TS=1 + a -DSF_CORR_TIMERS build prints the blocked build's phase timers."""
+argv: workload (sintel|kitti|spring) [clips] [reps].  Prints one JSON line per variant (us, algorithmic GB/s by SURVEY 8d)."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -61,19 +60,6 @@ if "blocked" in which:
     tb = timed(build)
     tl = timed(lambda: ops.corr_lookup_blocked(vol, cp, None, ko, B, pairs))
     res["blocked"] = (tb, tl)
-    if os.environ.get("SF_CORR_TS"):
-        ts = torch.zeros(131072 * 8, dtype=torch.int64, device=dev)
-        os.environ["SF_CORR_TS_BUF"] = str(ts.data_ptr())
-        build(); torch.cuda.synchronize()
-        os.environ.pop("SF_CORR_TS_BUF")
-        t = ts.view(-1, 8).cpu().double()
-        t = t[t[:, 0] > 0]
-        nt = t[:, 7].clamp(min=1)
-        for name, v in (("wave life", t[:, 2] - t[:, 0]), ("patch loads", t[:, 1]), ("tiles/wave", t[:, 7]), ("k-loops", t[:, 5]), ("epilogues", t[:, 6]),
-                        ("k-loop/tile", t[:, 5] / nt), ("epilogue/tile", t[:, 6] / nt)):
-            print(f"# {name:13s} mean {v.mean().item():9.0f} median {v.median().item():9.0f} min {v.min().item():9.0f} max {v.max().item():9.0f}")
-        dt_c, dt_r = t[:, 2] - t[:, 0], t[:, 4] - t[:, 3]
-        print(f"# clock: {(dt_c.sum() / dt_r.sum()).item() * 100:.0f} MHz")
 for k, (tb, tl) in res.items():
     it = 15
     frac = (b_bytes + it * l_bytes) / ((tb + it * tl) * 1e-6) / 8e12
