@@ -132,14 +132,15 @@ def _scratch(buf: Planes, n_img: int, rows: int, f16: bool = False, koct: bool =
     return Planes(buf.base, buf.off, rows_alloc * buf.P, n_img, rows, buf.P, f16=f16, koct=f16 and koct)
 
 
-def _handover(cx: ops.Ctx, buf: Planes, n_img: int, rows: int, P: int, consumer_rows: int, allow_koct: bool = True) -> Planes:
-    # (rows = K of the consuming layer, consumer_rows = its M)
-    """Scratch view for a tensor that is written by one GEMM and read only as the B operand of the next: fp32 planes in
-    the exact / f16x3 modes; in f16x2 fp16 values -- as k-octet planes when the consumer runs on the DMA-fed 128-row tile
-    (both of its operands then go HBM/L2 -> LDS without touching registers), as fp16 rows otherwise."""
+def _handover_format(cx: ops.Ctx, P: int, rows: int, consumer_rows: Optional[int] = None, allow_koct: bool = True) -> Tuple[bool, bool]:
+    """(f16, koct) of a tensor that is written by one kernel and read only as the B operand of the next GEMM (rows = K of that layer,
+    consumer_rows = its M): fp32 planes in the exact / f16x3 modes; in f16x2 fp16 values -- as k-octet planes when the consumer runs on
+    the DMA-fed 128-row tile (both of its operands then go HBM/L2 -> LDS without touching registers), as fp16 rows otherwise.
+    consumer_rows = None: the one reader is no GEMM (x2 -> depthwise, qkv -> temporal attention, v -> GMA pack): fp16 ROWS under x2_f16."""
     f16 = hidden_f16_ok(cx, P)
-    koct = f16 and allow_koct and ops.takes_koct(consumer_rows, rows) and cx.hidden_koct
-    return _scratch(buf, n_img, rows, f16=f16, koct=koct)
+    if consumer_rows is None:
+        return f16 and cx.x2_f16, False
+    return f16, f16 and allow_koct and ops.takes_koct(consumer_rows, rows) and cx.hidden_koct
 
 
 def _sub(X: Planes, i0: int, cnt: int) -> Planes:
@@ -162,66 +163,91 @@ def hidden_f16_ok(cx: ops.Ctx, P: int) -> bool:
     return cx.precision in (ops.PRECISION_F16X2, ops.PRECISION_F16) and P % 4 == 0 and cx.hidden_f16
 
 
+@dataclass(frozen=True)
+class SkRoute:
+    """What one SK block launches (update.py:30-36); chosen by resolve_skblock, nowhere else.  Formats: 'f32' planes, 'f16' = fp16
+    rows, 'koct' = fp16 k-octet planes; None = the tensor is never materialised (it stays in the registers of a fused launch)."""
+    front: str               # 'pair' = ffn1 + its epilogue as ONE sf_ffn_pair (mode 1); 'gemms' = ffn1.0, then ffn1.2 with the dw1x1 epilogue
+    back: str                # 'tail' = ONE sf_sk_tail; 'pair' = the pw GEMM, then sf_ffn_pair (mode 0); 'gemms' = pw, ffn2.0, ffn2.2
+    fold: bool               # pw_res (residual folded into the weights, residual-free epilogue) reads x3 as fp16 rows
+    x2: str                  # ffn1 -> depthwise K x K
+    x3: str                  # depthwise -> pw
+    x4: Optional[str]        # pw -> ffn2.0; None under 'tail'
+    hid1: Optional[str]      # ffn1.0 -> ffn1.2; None under a front 'pair'
+    hid2: Optional[str]      # ffn2.0 -> ffn2.2; None under 'tail' and a back 'pair'
+
+
+def resolve_skblock(W: SKBlockWeights, X: Planes, Y: Planes, cx: ops.Ctx) -> SkRoute:
+    """The route of one SK block from its weights, the DESCRIPTORS of its input and output planes (n_img, P, rows, f16, koct, group,
+    shadow present or not) and the context.  Host comparisons and the library's shape tables only: no device memory, no launch."""
+    C, P = W.c_in, X.P
+    name = lambda f16, koct: "koct" if koct else ("f16" if f16 else "f32")
+    fmt = lambda rows, consumer_rows=None, allow_koct=True: name(*_handover_format(cx, P, rows, consumer_rows, allow_koct))
+    view = lambda f: replace(X, rows=C, f16=f != "f32", koct=f == "koct", group=0, group_stride=0, shadow=None)   # (what _scratch hands out)
+    fills = X.n_img * P >= 4 * 7040       # enough pixels to fill the chip at 64 per workgroup (the measurements: at each rule below)
+    # fold: x3 in fp16 rows straight out of the depthwise kernel, residual folded into the pw weights: the pw GEMM reads half the bytes, has a
+    # residual-free epilogue and may therefore write k-octets.  x2 has ONE reader, the depthwise layer, whose two-product arithmetic multiplies
+    # fp16(x2) anyway: handed over as fp16 rows (half the bytes out of this GEMM and into the depthwise kernel, which then stages strips by DMA)
+    fold = hidden_f16_ok(cx, P) and cx.pw_fold
+    x2, x3 = (fmt(C), "f16") if fold else ("f32", "f32")
+    # (the flow head's pairs pay with enough pixels to fill the chip at 64 per workgroup: 8 clips 63.3 vs 63.8 ms per step, one
+    # clip 220 vs 226 ff/s the other way -- its GEMM launches split M for small grids)
+    head_pairs = bool(cx.head_pairs and X.group and X.shadow is not None and fills)
+    # the block input exists as k-octets only (operand AND residual) -- or it is the flow head's grouped view of the hidden state, whose k-octet copy
+    # is the operand and (round 5) the residual: the whole ffn1 + epilogue is one launch, the 1.5 C hidden tensor stays in registers (ffn_pair.hip)
+    pair1 = cx.ffn_pairs and x2 == "f16" and ((X.f16 and X.koct) or head_pairs) and ops.ffn_pair_ok(W.pair1, X, 1, cx)
+    front, hid1 = ("pair", None) if pair1 else ("gemms", fmt(W.c_mid, C))
+    # the back half as ONE launch: x4 and the 1.5 C hidden never leave the registers (csrc/sk_tail.hip; round 6).  Measured
+    # (profiles/r06_sk_tail_ab.txt, 24 images): 195 / 178 / 46 us against 218 / 219 / 58 us for the three launches at C = 256 / 256 /
+    # 128 -- used there; the flow head's shape (C = 384: one wave per SIMD for the registers) is 133 against 122 us, and a launch
+    # too small to fill the chip (a single clip) is faster as three launches whose grids split M: both keep the three launches
+    if fold and ops.sk_tail_ok(W.tail, view("f16"), Y, cx) and ((C <= 256 and fills) or cx.sk_tail_all):
+        return SkRoute(front, "tail", fold, x2, x3, None, hid1, None)
+    # x4 is read by ffn2.0 only: the same GEMM-to-GEMM hand-over as the hidden activations (x2 in `xa` is dead by now).  Unfolded: fp16 ROWS, not
+    # k-octets (their epilogue fetches its residual with 8 dword loads per octet and made the pw GEMMs 15-20 % slower -- more than their consumers gained)
+    x4 = fmt(C, W.c_mid, allow_koct=fold)
+    # (ffn2 pairs with hi + lo weights measured no faster than their two launches at C >= 256 -- 144 vs ~135 us at 256 -> 384 -> 192:
+    # twice the MFMAs on 16 x 16 x 32 tiles, whose fragment reads bind -- so those stay on the 32 x 32 x 16 kernels)
+    pair2_pays = (C <= 128 or W.pair2.products(cx) == (1, 1) or (W.c_out <= 16 and head_pairs)   # (the flow head: layer 2 is one 16-row tile)
+                  or (not fills and not X.group))    # (a small launch is latency-bound: one launch instead of two, +0.7 % on a single clip)
+    pair2 = cx.ffn_pairs and pair2_pays and x4 == "koct" and ops.ffn_pair_ok(W.pair2, view(x4), 0, cx) and (not Y.f16 or Y.koct)
+    return SkRoute(front, "pair" if pair2 else "gemms", fold, x2, x3, x4, hid1, None if pair2 else fmt(W.c_mid, W.c_out))
+
+
 def run_skblock(W: SKBlockWeights, X: Planes, Y: Planes, hid: Planes, xa: Planes, xb: Planes, h: int, w: int,
-                final_gelu: bool = False, cx: Optional[ops.Ctx] = None) -> None:
+                final_gelu: bool = False, cx: Optional[ops.Ctx] = None, route: Optional[SkRoute] = None) -> None:
     """One PCBlock4_Deep_nopool_res forward, op order of reference update.py:30-36:
     x1 = gelu(x + ffn1(x)); x2 = gelu(x1 + dw1x1(x1)); x3 = gelu(x2 + dwKxK(x2)); x4 = gelu(x3 + pw(x3));
-    y = ffn2(x4).  hid/xa/xb are scratch allocations (capacity >= n_img*c_mid / n_img*c_in rows)."""
+    y = ffn2(x4).  hid/xa/xb are scratch allocations (capacity >= n_img*c_mid / n_img*c_in rows).  Which launches, and the
+    format of every tensor between them, is `route` (default: resolve_skblock's)."""
     cx = ops._cx(cx)
     C = W.c_in
     assert X.rows == C and Y.rows == W.c_out and X.n_img == Y.n_img
-    a, b = _scratch(xa, X.n_img, C), _scratch(xb, X.n_img, C)
-    fold = hidden_f16_ok(cx, X.P) and cx.pw_fold
-    if fold and cx.x2_f16:
-        # x2 has ONE reader, the depthwise layer, whose two-product arithmetic multiplies fp16(x2) anyway: handed over as fp16
-        # rows (half the bytes out of this GEMM and into the depthwise kernel, which then stages its strips by DMA)
-        a = _scratch(xa, X.n_img, C, f16=True)
+    r = route or resolve_skblock(W, X, Y, cx)
+    view = lambda buf, rows, f: _scratch(buf, X.n_img, rows, f16=f != "f32", koct=f == "koct")
+    x2, x3 = view(xa, C, r.x2), view(xb, C, r.x3)
     # x1 = gelu(x + ffn1(x)); x2 = gelu(x1 + dw1x1(x1))  (both fused in the epilogue)
-    # (the flow head's pairs pay with enough pixels to fill the chip at 64 per workgroup: 8 clips 63.3 vs 63.8 ms per step, one
-    # clip 220 vs 226 ff/s the other way -- its GEMM launches split M for small grids)
-    head_pairs = cx.head_pairs and X.group and X.shadow is not None and X.n_img * X.P >= 4 * 7040
-    if cx.ffn_pairs and a.f16 and ((X.f16 and X.koct) or head_pairs) and ops.ffn_pair_ok(W.pair1, X, 1, cx):
-        # the block input exists as k-octets only (operand AND residual) -- or it is the flow head's grouped view of the hidden
-        # state, whose k-octet copy is the operand and (round 5) the residual: the whole ffn1 + epilogue is one launch, the 1.5 C
-        # hidden tensor stays in registers (csrc/ffn_pair.hip)
-        ops.ffn_pair(W.pair1, X, a, 1, dw_w=W.dw1_w, dw_b=W.dw1_b, cx=cx)
+    if r.front == "pair":
+        ops.ffn_pair(W.pair1, X, x2, 1, dw_w=W.dw1_w, dw_b=W.dw1_b, cx=cx)
     else:
-        hidden = _handover(cx, hid, X.n_img, W.c_mid, X.P, consumer_rows=C)         # ffn1.0 -> ffn1.2
+        hidden = view(hid, W.c_mid, r.hid1)                                         # ffn1.0 -> ffn1.2
         ops.gemm(W.ffn1_0, X, hidden, EPI_GELU, cx=cx)
-        ops.gemm(W.ffn1_2, hidden, a, EPI_RES_GELU_DW1, R=X, dw_w=W.dw1_w, dw_b=W.dw1_b, cx=cx)
-    # x4 is read by ffn2.0 only: the same GEMM-to-GEMM hand-over as the hidden activations (x2 in `xa` is dead by now)
-    if fold:
-        # x3 in fp16 rows straight out of the depthwise kernel, residual folded into the pw weights: the pw GEMM reads half
-        # the bytes, has a residual-free epilogue and may therefore write k-octets
-        b16 = _scratch(xb, X.n_img, C, f16=True)
-        ops.dwconv_res_gelu(a, W.dwk_w, W.dwk_b, b16, h, w, W.k, single=W.dw_single, cx=cx)   # x3 = gelu(x2 + dwKxK(x2))
-        # the back half as ONE launch: x4 and the 1.5 C hidden never leave the registers (csrc/sk_tail.hip; round 6).  Measured
-        # (profiles/r06_sk_tail_ab.txt, 24 images): 195 / 178 / 46 us against 218 / 219 / 58 us for the three launches at C = 256 / 256 /
-        # 128 -- used there; the flow head's shape (C = 384: one wave per SIMD for the registers) is 133 against 122 us, and a launch
-        # too small to fill the chip (a single clip) is faster as three launches whose grids split M: both keep the three launches
-        if (ops.sk_tail_ok(W.tail, b16, Y, cx) and W.c_in <= 256 and X.n_img * X.P >= 4 * 7040) or \
-                (cx.sk_tail_all and ops.sk_tail_ok(W.tail, b16, Y, cx)):
-            ops.sk_tail(W.tail, b16, Y, gelu_out=final_gelu, cx=cx)
-            return
-        a4 = _handover(cx, xa, X.n_img, C, X.P, consumer_rows=W.c_mid)
-        ops.gemm(W.pw_res, b16, a4, EPI_GELU, cx=cx)                            # x4 = gelu((pw + I) x3)
+        ops.gemm(W.ffn1_2, hidden, x2, EPI_RES_GELU_DW1, R=X, dw_w=W.dw1_w, dw_b=W.dw1_b, cx=cx)
+    ops.dwconv_res_gelu(x2, W.dwk_w, W.dwk_b, x3, h, w, W.k, single=W.dw_single, cx=cx)   # x3 = gelu(x2 + dwKxK(x2))
+    if r.back == "tail":
+        ops.sk_tail(W.tail, x3, Y, gelu_out=final_gelu, cx=cx)                      # y = ffn2(gelu((pw + I) x3)): one launch
     else:
-        ops.dwconv_res_gelu(a, W.dwk_w, W.dwk_b, b, h, w, W.k, single=W.dw_single, cx=cx)   # x3 = gelu(x2 + dwKxK(x2))
-        # (fp16 ROWS, not k-octets: the k-octet epilogue fetches its residual with 8 dword loads per octet and made the
-        # pw GEMMs 15-20 % slower -- more than their consumers gained)
-        a4 = _handover(cx, xa, X.n_img, C, X.P, consumer_rows=W.c_mid, allow_koct=False)
-        ops.gemm(W.pw, b, a4, EPI_RES_GELU, R=b, cx=cx)                         # x4 = gelu(x3 + pw(x3))
-    # (ffn2 pairs with hi + lo weights measured no faster than their two launches at C >= 256 -- 144 vs ~135 us at 256 -> 384 -> 192:
-    # twice the MFMAs on 16 x 16 x 32 tiles, whose fragment reads bind -- so those stay on the 32 x 32 x 16 kernels)
-    pair2_pays = W.c_in <= 128 or W.pair2.products(cx) == (1, 1) or (W.c_out <= 16 and head_pairs)   # (the flow head: layer 2 is one 16-row tile)
-    if X.n_img * X.P < 4 * 7040 and not X.group:            # (a small launch is latency-bound: one launch instead of two, +0.7 % on a single clip)
-        pair2_pays = True
-    if (cx.ffn_pairs and pair2_pays and a4.f16 and a4.koct and ops.ffn_pair_ok(W.pair2, a4, 0, cx) and (not Y.f16 or Y.koct)):
-        ops.ffn_pair(W.pair2, a4, Y, 0, gelu_out=final_gelu, cx=cx)                 # y = ffn2(x4): one launch
-        return
-    hidden = _handover(cx, hid, X.n_img, W.c_mid, X.P, consumer_rows=W.c_out)       # ffn2.0 -> ffn2.2
-    ops.gemm(W.ffn2_0, a4, hidden, EPI_GELU, cx=cx)
-    ops.gemm(W.ffn2_2, hidden, Y, EPI_GELU if final_gelu else EPI_NONE, cx=cx)
+        x4 = view(xa, C, r.x4)
+        if r.fold:
+            ops.gemm(W.pw_res, x3, x4, EPI_GELU, cx=cx)                             # x4 = gelu((pw + I) x3)
+        else:
+            ops.gemm(W.pw, x3, x4, EPI_RES_GELU, R=x3, cx=cx)                       # x4 = gelu(x3 + pw(x3))
+        if r.back == "pair":
+            ops.ffn_pair(W.pair2, x4, Y, 0, gelu_out=final_gelu, cx=cx)             # y = ffn2(x4): one launch
+        else:
+            hidden = view(hid, W.c_mid, r.hid2)                                     # ffn2.0 -> ffn2.2
+            ops.gemm(W.ffn2_0, x4, hidden, EPI_GELU, cx=cx)
+            ops.gemm(W.ffn2_2, hidden, Y, EPI_GELU if final_gelu else EPI_NONE, cx=cx)
 
 
 class HotPathWeights:
@@ -617,7 +643,7 @@ class HotPathEngine:
             v128 = None
         else:
             # v has ONE reader, the pack of the fused kernel (which rounds it to fp16): fp16 rows where the fp16 hand-over is active
-            v128 = _scratch(pl.v128, n, HDIM, f16=True) if (hidden_f16_ok(cx, P) and cx.x2_f16) else pl.v128
+            v128 = _scratch(pl.v128, n, HDIM, *_handover_format(cx, P, HDIM))
             ops.gemm(W.to_v, pl.mf, v128, EPI_NONE, cx=cx)
         if g.form == "stored":
             # the stored weights streamed past v (gma.py:99-102): half the matrix-core work of the recompute, HBM-bound
@@ -749,17 +775,18 @@ class HotPathEngine:
                 ops.temporal_block(W.temporal, pl.mf, pl.mft, Pn, (W.ln1_w, W.ln1_b), (W.ln2_w, W.ln2_b), cx=cs)
             else:
                 # LayerNorm / attention outputs have ONE reader, a GEMM: in the f16x2 mode they leave as its k-octet operand
-                ko = lambda buf, M: (lambda t: t if t.koct else buf)(_handover(cs, buf, pl.n, HDIM, P, consumer_rows=M))
+                hand = lambda buf, rows, M=None: _scratch(buf, pl.n, rows, *_handover_format(cs, P, rows, M))
+                ko = lambda buf, M: (lambda t: t if t.koct else buf)(hand(buf, HDIM, M))
                 ln, att = ko(pl.ln128, W.qkv.M), ko(pl.att128, W.proj.M)
                 ops.layernorm_cm(pl.mf, W.ln1_w, W.ln1_b, ln)
                 # qkv has ONE reader, the attention core: fp16 rows where the fp16 hand-over is active (EPE-neutral)
-                qkv = _scratch(pl.qkv, pl.n, 3 * HDIM, f16=True) if (hidden_f16_ok(cs, P) and cs.x2_f16) else pl.qkv
+                qkv = hand(pl.qkv, 3 * HDIM)
                 ops.gemm(W.qkv, ln, qkv, EPI_NONE, cx=cs)
                 ops.temporal_attn(qkv, att, Bc, Pn, HDIM)
                 ops.gemm(W.proj, att, pl.tx128, EPI_RES, R=pl.mf, cx=cs)
                 ln = ko(pl.ln128, W.fc1.M)
                 ops.layernorm_cm(pl.tx128, W.ln2_w, W.ln2_b, ln)
-                h256 = _handover(cs, pl.h256, pl.n, 256, P, consumer_rows=HDIM)        # fc1 -> fc2 only
+                h256 = hand(pl.h256, 256, HDIM)                                        # fc1 -> fc2 only
                 ops.gemm(W.fc1, ln, h256, EPI_GELU, cx=cs)
                 ops.gemm(W.fc2, h256, pl.mft, EPI_RES, R=pl.tx128, cx=cs)
         # a7: global aggregation (main stream).  options.gma_per_chain: the recompute kernel as one launch per half-batch chain (each

@@ -623,3 +623,56 @@ def test_corr_block_scratch(dev, hw, dtype, layout):
     a, b = _both(call)
     _assert_bytes(a, b, f"CorrBlock {layout} {dtype} {hw}")
     assert all(np.isfinite(t.astype(np.float32)).all() for t in a) and a[0].shape == (2, 324, h, w)
+
+
+# ---- F. the SK block launches what its route says --------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("flags,front,back", [({}, "pair", "pair"), ({"sk_tail_all": True}, "pair", "tail"),
+                                              ({"ffn_pairs": False, "sk_tail": False}, "gemms", "gemms")])
+def test_skblock_issues_the_calls_of_its_route(dev, monkeypatch, flags, front, back):
+    """A 128 -> 64 block at 2 images of 8 x 8 from a k-octet-only input, f16x2: the C-ABI calls of engine.run_skblock are those of
+    engine.resolve_skblock's route -- the default context (a small launch: pair + pw + pair), sk_tail_all (pair + tail) and with both
+    fused forms off (five GEMMs) cover every value of front and back.  Each output against torch in float64 within the bound
+    tests/test_gpu_parity.py::test_skblock_pw_fold_vs_float64 sets for this block in this mode."""
+    import torch.nn.functional as F
+    from streamflow_amd import _lib, ops
+    from streamflow_amd.engine import SKBlockWeights, resolve_skblock, run_skblock
+    from streamflow_amd.ops import Planes
+    C, Cm, Co, k, n, h, w = 128, 192, 64, 15, 2, 8, 8
+    P = h * w
+    if "skblock" not in _CACHE:
+        g = torch.Generator().manual_seed(C + k)
+        r = lambda *s: torch.randn(*s, generator=g)
+        sd = {"b.ffn1.0.weight": r(Cm, C, 1, 1) / C ** 0.5, "b.ffn1.0.bias": r(Cm) * 0.1,
+              "b.ffn1.2.weight": r(C, Cm, 1, 1) / Cm ** 0.5, "b.ffn1.2.bias": r(C) * 0.1,
+              "b.conv_list.0.weight": r(C, 1, 1, 1) * 0.3, "b.conv_list.0.bias": r(C) * 0.1,
+              "b.conv_list.1.weight": r(C, 1, k, k) / k, "b.conv_list.1.bias": r(C) * 0.1,
+              "b.pw.weight": r(C, C, 1, 1) / C ** 0.5, "b.pw.bias": r(C) * 0.1,
+              "b.ffn2.0.weight": r(Cm, C, 1, 1) / C ** 0.5, "b.ffn2.0.bias": r(Cm) * 0.1,
+              "b.ffn2.2.weight": r(Co, Cm, 1, 1) / Cm ** 0.5, "b.ffn2.2.bias": r(Co) * 0.1}
+        x = r(n, C, h, w)
+        d = {kk: v.double() for kk, v in sd.items()}
+        c1 = lambda t, nm: F.conv2d(t, d["b." + nm + ".weight"], d["b." + nm + ".bias"])
+        t = F.gelu(x.double() + c1(F.gelu(c1(x.double(), "ffn1.0")), "ffn1.2"))
+        t = F.gelu(t + F.conv2d(t, d["b.conv_list.0.weight"], d["b.conv_list.0.bias"], groups=C))
+        t = F.gelu(t + F.conv2d(t, d["b.conv_list.1.weight"], d["b.conv_list.1.bias"], padding=k // 2, groups=C))
+        t = F.gelu(t + c1(t, "pw"))
+        _CACHE["skblock"] = (SKBlockWeights(sd, "b", dev), x, c1(F.gelu(c1(t, "ffn2.0")), "ffn2.2").view(n, Co, P))
+    W, x, ref = _CACHE["skblock"]
+    x32 = Planes.of(x.view(n, C, P).to(dev))
+    X = ops.new_shadow(x32, dev)                         # the block input as fp16 k-octet planes only
+    ops.pack_koct(x32, X)
+    y = torch.full((n, Co, P), float("nan"), device=dev)
+    mk = lambda rows: Planes.of(torch.zeros(n, rows + 8, P, device=dev))
+    cx = ops.Ctx(ops.PRECISION_F16X2, **flags)
+    route = resolve_skblock(W, X, Planes.of(y), cx)
+    assert (route.front, route.back) == (front, back)
+    calls, check = [], _lib.check
+    monkeypatch.setattr(_lib, "check", lambda status, what="": (calls.append(what), check(status, what))[1])
+    run_skblock(W, X, Planes.of(y), mk(Cm), mk(C), mk(C), h, w, cx=cx)
+    torch.cuda.synchronize()
+    want = {"pair": ["sf_ffn_pair"], "gemms": ["sf_gemm", "sf_gemm"]}[front] + ["sf_dwconv_res_gelu_f16in"]
+    want += {"tail": ["sf_sk_tail"], "pair": ["sf_gemm", "sf_ffn_pair"], "gemms": ["sf_gemm", "sf_gemm", "sf_gemm"]}[back]
+    assert calls == want
+    err, scale = (y.double().cpu() - ref).abs().max().item(), ref.abs().max().item()
+    assert err < 4e-3 * scale, (err, scale)
