@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 133
+#define SF_VERSION 134
 
 enum {
     SF_OK = 0,
@@ -916,6 +916,59 @@ int64_t sf_png_encode_ws_bytes(int n_images, int h, int w, int bpp);
 int sf_png_encode(const uint8_t* img, int64_t img_image_stride, int64_t img_row_stride, int n_images, int h, int w, int bpp,
                   int swap16, uint8_t* out, int64_t out_image_stride, int64_t* out_bytes, void* ws, int64_t ws_bytes, void* stream);
 int sf_flow_to_kitti16(const float* flow, uint16_t* out, int n, int h, int w, void* stream);
+
+/* ---- JPEG output: baseline sequential DCT, Huffman coding (ITU-T T.81) of a batch of device images; the frames of a Motion-JPEG video ----
+ * sf_jpeg_encode: image i is h rows of w pixels at img + i img_image_stride + y img_row_stride; channels = 3: interleaved R, G, B bytes
+ *   (what sf_flow_to_image writes), channels = 1: grey.  qtables is HOST memory: [2][64] quantisation steps 1 .. 255 in natural (row-major)
+ *   order, table 0 for luma / grey and table 1 for chroma; they are read before the call returns.  out + i out_image_stride receives
+ *   image i's entropy-coded segment -- everything between the SOS header and EOI -- and out_bytes[i] (device memory) its length; the
+ *   host writes the marker segments around it (jpeg_gpu.jpeg_file).  The format:
+ *   Colour.  Grey is one component.  RGB becomes JFIF YCbCr (BT.601, full range) in 16-bit fixed point, >> arithmetic:
+ *       Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *       Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16          (8421375 = 128 x 65536 + 32767)
+ *       Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16
+ *     all in 0 .. 255.  Sampling is 4:4:4: H = V = 1 for every component, an MCU is one 8 x 8 block per component in the order Y, Cb, Cr.
+ *   Edges.  Where w or h is no multiple of 8 the last column / row is replicated.
+ *   DCT.  s = sample - 128.  Table C[u][x] = round(2^13 sqrt 2 c(u) / 2 cos((2 x + 1) u pi / 16)), c(0) = 1 / sqrt 2, c(u) = 1 otherwise: the
+ *     values 4096 (u = 0, 4: exact), 5681 4816 3218 1130 (cos of 1, 3, 5, 7 pi / 16), 5352 2217 (2, 6 pi / 16) with the cosines' signs;
+ *     the factor sqrt 2 per pass makes the two passes give 2 F, and the DC coefficient exact.  Rows first:
+ *     t[y][u] = (sum_x C[u][x] s[y][x] + 256) >> 9 (4 fraction bits, rounded half up); then columns: G[v][u] = sum_y C[v][y] t[y][u]
+ *     = 2^18 F[v][u], not rounded.  All sums are exact in 32 bits: |G| < 2^29.
+ *     Accuracy: G / 2^18 is within B = 0.3126 of the exact DCT coefficient.  With e = 2^-14 the table's rounding error relative to 2^13
+ *     and A = max_u sum_x |sqrt 2 c(u) / 2 cos(..)| = 4: |t - sqrt 2 t_exact| <= 8 x 128 e + 2^-5 = 0.09375 =: d (table, then rounding),
+ *     and |G / 2^17 - 2 F_exact| <= A d + 8 e (128 A + d) = 0.375 + 0.25005, half of which is B.
+ *   Quantisation.  level = sign(G) ((|G| + (q << 17)) / (q << 18)), integer division: G / (2^18 q) rounded half away from zero, q the step of
+ *     the component's table at that coefficient.  |level| <= 1024 for DC (a DC difference has category <= 11) and <= 1020 for AC
+ *     (category <= 10): an AC basis function sums to zero and its absolute values sum to at most 8, so |F_exact| <= 4 (128 + 127).
+ *   Entropy coding.  The four typical Huffman tables of T.81 Annex K.3 (K.3 / K.4 for DC, K.5 / K.6 for AC), luma tables for Y / grey and
+ *     chroma tables for Cb, Cr; canonical codes as in Annex C.  A block: the DC difference to the previous block of the same component as
+ *     category code + category bits (negative values: the low bits of value - 1); the AC levels along the zigzag scan as (run << 4 |
+ *     category) code + category bits, ZRL (0xF0) for every 16 zeros in front of a level, EOB (0x00) unless coefficient 63 is non-zero.
+ *     Bits are written MSB first.
+ *   Restart intervals.  One interval per MCU row: DRI = ceil(w / 8).  The DC predictions are 0 at the start of each; each is padded to a
+ *     byte with 1-bits; every 0xFF byte of it (a padded one too) is followed by 0x00; RSTm = FF D0+m, m = row mod 8, stands between
+ *     intervals, none behind the last.  tests/jpeg_cases.py restates all of it; the output equals that restatement byte for byte, and two
+ *     runs are bitwise equal.
+ * sf_jpeg_encode_bound(h, w, channels): no segment is longer, whatever the image and the tables hold: ceil(h / 8) (2 I + 2) rounded up to a
+ *   multiple of 4, I = ceil(ceil(w / 8) channels 1660 / 8).  A block has at most 1660 bits: the longest DC code (11 bits, chroma
+ *   category 11) + 11 bits, and 63 AC levels of the longest AC code (16 bits) + 10 bits (a ZRL or EOB is cheaper than the levels it
+ *   stands for); I is an interval's bytes, doubled for stuffing, + 2 for its marker.  -1 for h or w outside 1 .. SF_JPEG_MAX_DIM or
+ *   channels outside {1, 3}.  The bytes of a slot behind the segment are not written (`out` need not be cleared), nor anything beyond
+ *   the bound.
+ * sf_jpeg_encode_ws_bytes: the workspace (levels, the intervals before stuffing, their lengths and offsets); -1 for a refused shape or n.
+ * Five launches (DCT: a thread per block; pack: a workgroup per interval, a thread per block and component, the bits ORed with vector
+ *   atomics into workspace words the same workgroup cleared; 0xFF count; offsets: a thread per image; gather with stuffing: plain byte
+ *   stores); dependencies between workgroups are launch boundaries.  No host synchronisation.
+ *   SF_ERR_BAD_ARG before any launch for: null pointers, n_images outside 1 .. 65535, h or w < 1, channels outside {1, 3}, a table entry
+ *   outside 1 .. 255, img_row_stride < w channels, img_image_stride < (h - 1) img_row_stride + w channels, out_image_stride below the
+ *   bound, out or out_image_stride not a multiple of 4, out_bytes not 8-byte aligned, ws_bytes too small.  SF_ERR_UNSUPPORTED for h or w
+ *   above SF_JPEG_MAX_DIM (checked after the first five of these). */
+#define SF_JPEG_MAX_DIM 8192 /* the bound of an 8192 x 8192 x 3 image stays below 2^31; 2160 x 3840 video frames fit */
+int64_t sf_jpeg_encode_bound(int h, int w, int channels);
+int64_t sf_jpeg_encode_ws_bytes(int n_images, int h, int w, int channels);
+int sf_jpeg_encode(const uint8_t* img, int64_t img_image_stride, int64_t img_row_stride, int n_images, int h, int w, int channels,
+                   const uint16_t* qtables, uint8_t* out, int64_t out_image_stride, int64_t* out_bytes, void* ws, int64_t ws_bytes,
+                   void* stream);
 
 /* ---- Spring .flo5 output: the HDF5 filters shuffle -> deflate of a batch of flow fields, chunk by chunk (flo5.flo5_file frames them) ---
  * sf_flo5_encode: field i is two planes, element (ch, y, x) at flow + i field_stride + ch ch_stride + y row_stride + x (strides in

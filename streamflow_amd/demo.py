@@ -1,5 +1,6 @@
-"""Clip grouping of the reference's demo pipeline (demo.py:502-534) and its `vis_flow` (demo.py:536-548), without its video I/O
-(decord / cv2): frames come in as tensors and the colour-wheel images leave as a PNG sequence.
+"""Clip grouping of the reference's demo pipeline (demo.py:502-534) and its `vis_flow` (demo.py:536-548), without its video input
+(decord / cv2): frames come in as tensors and the colour-wheel images leave as a PNG sequence (`vis_flow`) or as one Motion-JPEG
+AVI file encoded on the GPU (`vis_flow_video`).
 
 The demo slides a window of T frames with stride T-1 over the video; the last window re-uses the final T frames
 and drops the flow fields that an earlier window already produced (``flags == -1``).  Every consecutive frame pair
@@ -114,11 +115,11 @@ def write_colour_pngs(flows: Sequence[torch.Tensor], paths: Sequence[str], rad_m
 
 
 def vis_flow(flows_result: Sequence[torch.Tensor], save_dir: str = "flow_result", rad_max=None, png_encode: str = "host") -> List[str]:
-    """The reference's `vis_flow` (demo.py:536-548) with a PNG sequence ``save_dir/frame_%04d.png`` in place of its mp4 (no video
-    encoder here).  flows_result: flow fields [2, H, W] as `predict_frames` returns them (CPU tensors are moved to the current
-    GPU: the colouring is the sf_flow_to_image kernel, all fields of equal shape in one call).  `rad_max` fixes one scale for the
-    whole sequence (no flicker between frames); default: each frame on its own scale, as the reference.  png_encode="gpu": the files
-    are encoded on the GPU too (write_colour_pngs).  Returns the paths."""
+    """The reference's `vis_flow` (demo.py:536-548) with a PNG sequence ``save_dir/frame_%04d.png`` in place of its mp4
+    (`vis_flow_video` writes the single video file).  flows_result: flow fields [2, H, W] as `predict_frames` returns them (CPU
+    tensors are moved to the current GPU: the colouring is the sf_flow_to_image kernel, all fields of equal shape in one call).
+    `rad_max` fixes one scale for the whole sequence (no flicker between frames); default: each frame on its own scale, as the
+    reference.  png_encode="gpu": the files are encoded on the GPU too (write_colour_pngs).  Returns the paths."""
     import os
     os.makedirs(save_dir, exist_ok=True)
     paths = [os.path.join(save_dir, "frame_%04d.png" % i) for i in range(len(flows_result))]
@@ -126,18 +127,49 @@ def vis_flow(flows_result: Sequence[torch.Tensor], save_dir: str = "flow_result"
     return paths
 
 
+def _add_video_frames(writer, flows: Sequence[torch.Tensor], rad_max, quality: int) -> None:
+    """The colour-wheel images of `flows` as JPEG frames of `writer`, in order; a field of another shape than the video: ValueError."""
+    from . import jpeg_gpu
+    frames: List = [None] * len(flows)
+    for idx, batch in _colour_batches(flows, rad_max):
+        if (int(batch.shape[2]), int(batch.shape[1])) != (writer.width, writer.height):
+            raise ValueError(f"vis_flow_video: a field of {int(batch.shape[2])} x {int(batch.shape[1])} in a video of "
+                             f"{writer.width} x {writer.height}")
+        for i, blob in zip(idx, jpeg_gpu.encode_batch(batch, quality=quality)):
+            frames[i] = blob
+    for blob in frames:
+        writer.add(blob)
+
+
+def vis_flow_video(flows_result: Sequence[torch.Tensor], save_path: str = "flow_result.avi", fps: float = 8, rad_max=None,
+                   quality: int = 90) -> str:
+    """The reference's `vis_flow` (demo.py:536-548) with its signature and default fps: every field coloured (sf_flow_to_image),
+    encoded as a baseline JPEG on the GPU (jpeg_gpu.encode_batch, IJG quality `quality`, 4:4:4) and written as one Motion-JPEG AVI
+    file (avi.MjpegWriter) in place of the reference's mp4.  All fields must share one shape (ValueError).  `rad_max` fixes one
+    colour scale for the whole video.  Returns save_path."""
+    from . import avi, jpeg_gpu
+    if not flows_result:
+        raise ValueError("vis_flow_video: no flow fields")
+    jpeg_gpu.quant_tables(quality)                                       # a bad quality fails before the file exists
+    h, w = (int(v) for v in flows_result[0].shape[-2:])
+    with avi.MjpegWriter(save_path, w, h, fps) as writer:
+        _add_video_frames(writer, flows_result, rad_max, quality)
+    return save_path
+
+
 def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, clips_per_step: int = 8, mode: str = "sintel",
                                   save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host",
-                                  png_encode: str = "host") -> int:
+                                  png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90) -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames: video.FrameDir ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
     are coloured on the GPU and written as ``save_dir/frame_%04d.png`` (numbered by pair) and, with `flo_dir`, as Middlebury
     ``flo_dir/frame_%04d.flo``.  png_decode="gpu": the frames' PNG rows are unfiltered on the GPU (video.FrameDir(decode="gpu")), the
     same bytes as the host decoder's.  png_encode="gpu": the colour images are filtered and deflated on the GPU
-    (png_gpu.encode_batch: no uncompressed image crosses to the host; the same pixels, other file bytes).  Runs on the current GPU.
-    Returns the number of pairs."""
+    (png_gpu.encode_batch: no uncompressed image crosses to the host; the same pixels, other file bytes).  With `video_path` every
+    batch's images are also encoded as JPEG frames on the GPU (IJG quality `jpeg_quality`) and appended to one Motion-JPEG AVI file
+    of `fps` frames per second (avi.MjpegWriter).  Runs on the current GPU.  Returns the number of pairs."""
     import os
-    from . import flow_io, video
+    from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
     _check_png_encode(png_encode)
     frames = video.FrameDir(path, decode=png_decode)
@@ -149,6 +181,9 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
         if d:
             os.makedirs(d, exist_ok=True)
     written = [0]
+    if video_path:
+        jpeg_gpu.quant_tables(jpeg_quality)
+    writer = []                                                          # opened by the first batch, which knows the frame size
 
     def sink(first_pair: int, flows: torch.Tensor) -> None:
         names = ["frame_%04d" % (first_pair + k) for k in range(flows.shape[0])]
@@ -159,19 +194,31 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
             host = flows.cpu().numpy()
             for k, name in enumerate(names):
                 flow_io.write_flo(os.path.join(flo_dir, name + ".flo"), host[k].transpose(1, 2, 0))
+        if video_path:
+            if not writer:
+                writer.append(avi.MjpegWriter(video_path, int(flows.shape[-1]), int(flows.shape[-2]), fps))
+            _add_video_frames(writer[0], list(flows), rad_max, jpeg_quality)
         written[0] += int(flows.shape[0])
 
-    video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink)
+    try:
+        video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink)
+    finally:
+        if writer:
+            writer[0].close()
     return written[0]
 
 
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m streamflow_amd.demo",
-                                 description="Flow fields of a directory of PNG frames, as colour-wheel PNGs (and .flo files)")
+                                 description="Flow fields of a directory of PNG frames, as colour-wheel PNGs, a Motion-JPEG AVI "
+                                             "video and .flo files")
     ap.add_argument("--frames", required=True, help="directory of PNG frames (sorted by name)")
     ap.add_argument("--ckpt", required=True, help="StreamFlow checkpoint")
-    ap.add_argument("--out", required=True, help="directory for frame_%%04d.png")
+    ap.add_argument("--out", default=None, help="directory for frame_%%04d.png (may be left out only with --video)")
+    ap.add_argument("--video", default=None, help="one Motion-JPEG AVI file of the colour-wheel images, encoded on the GPU")
+    ap.add_argument("--fps", type=float, default=8, help="frames per second of --video")
+    ap.add_argument("--jpeg-quality", type=int, default=90, help="IJG quality 1 .. 100 of the frames of --video")
     ap.add_argument("--flo", default=None, help="directory for frame_%%04d.flo")
     ap.add_argument("--T", type=int, default=4)
     ap.add_argument("--iters", type=int, default=15)
@@ -183,10 +230,12 @@ def main(argv=None) -> int:
                     help="where the colour images are filtered and deflated (the same pixels either way, other file bytes)")
     ap.add_argument("--rad-max", type=float, default=None, help="one colour scale for the whole video (default: per frame)")
     a = ap.parse_args(argv)
+    if not a.out and not a.video:
+        ap.error("the following arguments are required: --out (or --video)")
     n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
                                       save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode,
-                                      png_encode=a.png_encode)
-    print(f"{n} flow fields -> {a.out}" + (f", {a.flo}" if a.flo else ""))
+                                      png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality)
+    print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo) if d))
     return 0
 
 

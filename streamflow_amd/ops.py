@@ -13,6 +13,7 @@ import os
 from dataclasses import dataclass, replace
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1487,6 +1488,41 @@ def png_encode(images: torch.Tensor):
     _lib.check(lib.sf_png_encode(images.data_ptr(), image_stride * size, images.stride(1) * size, n, h, w, c * size, 1 if size == 2 else 0,
                                  streams.data_ptr(), bound, lengths.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream()), "sf_png_encode")
     return streams, lengths
+
+
+@on_tensor_device
+def jpeg_encode(images: torch.Tensor, qtables):
+    """The entropy-coded segments of baseline JPEG files for a batch of device images (sf_jpeg_encode: JFIF YCbCr 4:4:4, integer DCT,
+    the Annex K.3 Huffman tables, one restart interval per MCU row, csrc/jpeg_encode.hip; the host half is jpeg_gpu.jpeg_file):
+    images uint8 [n, H, W, 3] (RGB) or [n, H, W] (grey) on the GPU, the samples of a row contiguous, any row and image strides;
+    qtables: [2, 64] steps 1 .. 255 in natural order (jpeg_gpu.quant_tables).  Returns (segments uint8 [n, sf_jpeg_encode_bound],
+    lengths int64 [n]) on the same GPU: segment i is segments[i, :lengths[i]], the bytes behind it are unspecified.  Enqueued on the
+    current stream, no synchronisation."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda:
+        raise RuntimeError(f"jpeg_encode: images must be on the GPU (got {getattr(images, 'device', type(images).__name__)}); "
+                           "there is no CPU fallback")
+    if images.dtype != torch.uint8 or images.dim() not in (3, 4) or images.numel() == 0 or (images.dim() == 4 and images.shape[3] != 3):
+        raise RuntimeError(f"jpeg_encode: expected uint8 [n, H, W, 3] or [n, H, W], got {images.dtype} {tuple(images.shape)}")
+    n, h, w = (int(v) for v in images.shape[:3])
+    c = 3 if images.dim() == 4 else 1
+    if (c == 3 and images.stride(3) != 1) or images.stride(2) != c or images.stride(1) < w * c or \
+            (n > 1 and images.stride(0) < (h - 1) * images.stride(1) + w * c):
+        raise RuntimeError(f"jpeg_encode: the samples of a row must be contiguous and rows / images must not overlap (strides {images.stride()})")
+    q = np.ascontiguousarray(np.asarray(qtables)).reshape(-1)
+    if q.size != 128 or q.min() < 1 or q.max() > 255:
+        raise RuntimeError("jpeg_encode: qtables must be two tables of 64 steps in 1 .. 255")
+    q = q.astype(np.uint16)
+    lib = _lib.load()
+    bound, ws_bytes = lib.sf_jpeg_encode_bound(h, w, c), lib.sf_jpeg_encode_ws_bytes(n, h, w, c)
+    if bound < 0 or ws_bytes < 0:
+        raise RuntimeError(f"jpeg_encode: n = {n}, h = {h}, w = {w} is outside what sf_jpeg_encode takes")
+    segments = torch.empty(n, bound, dtype=torch.uint8, device=images.device)
+    lengths = torch.empty(n, dtype=torch.int64, device=images.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=images.device)
+    image_stride = images.stride(0) if n > 1 else (h - 1) * images.stride(1) + w * c
+    _lib.check(lib.sf_jpeg_encode(images.data_ptr(), image_stride, images.stride(1), n, h, w, c, q.ctypes.data, segments.data_ptr(), bound,
+                                  lengths.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream()), "sf_jpeg_encode")
+    return segments, lengths
 
 
 @on_tensor_device
