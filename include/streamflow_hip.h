@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 134
+#define SF_VERSION 135
 
 enum {
     SF_OK = 0,
@@ -969,6 +969,88 @@ int64_t sf_jpeg_encode_ws_bytes(int n_images, int h, int w, int channels);
 int sf_jpeg_encode(const uint8_t* img, int64_t img_image_stride, int64_t img_row_stride, int n_images, int h, int w, int channels,
                    const uint16_t* qtables, uint8_t* out, int64_t out_image_stride, int64_t* out_bytes, void* ws, int64_t ws_bytes,
                    void* stream);
+
+/* ---- JPEG input: baseline files of one geometry -> device images (csrc/jpeg_decode.hip; the host's marker walk is jpeg_gpu.parse) ----
+ * sf_jpeg_decode: n_images files of ONE geometry -- h, w, components (1: grey, 3: YCbCr), luma sampling hs x vs in {1x1, 2x1, 2x2} with
+ *   chroma at 1 x 1 (4:4:4, 4:2:2, 4:2:0; grey: 1 x 1) -- from their entropy-coded bytes to pixels.  Baseline sequential DCT (SOF0), 8 bit,
+ *   Huffman, one interleaved scan; whatever else a file may be is the host parser's to refuse.  All pointers but `stream` are device
+ *   memory:
+ *   data     data_bytes bytes: the entropy-coded bytes of all files, still stuffed (FF 00), any alignment.
+ *   desc     n_intervals rows of SF_JPEG_DESC_WORDS int64, one per restart interval: in_off, in_len (the interval is data[in_off ..
+ *            in_off + in_len): no RSTm marker, no fill bytes), image, first_mcu, n_mcus (the MCUs first_mcu .. first_mcu + n_mcus - 1 of
+ *            that image, counted in scan order: rows of ceil(w / 8 hs) MCUs), table_set.  A file without DRI is one interval with all
+ *            its MCUs.  The intervals of an image must cover each of its MCUs once.
+ *   tables   n_table_sets records of SF_JPEG_TABLE_SET_BYTES = 3 x 608 bytes, de-duplicated by the host: per component (3 slots, the
+ *            unused ones of a grey file are not read) 64 quantisation steps as bytes in NATURAL (row-major) order, then the DC and the
+ *            AC Huffman specification, each 16 BITS bytes + 256 HUFFVAL bytes (fixed stride: entries past the sum of BITS are ignored).
+ *   out      image i at out + i out_image_stride + y out_row_stride, w pixels of out_channels bytes: 3: R, G, B (a grey file's sample
+ *            three times, as datasets.read_frame does for grey PNGs), 1: the grey sample (components = 1 only).
+ *   status   one int32 per image: 0, or the SF_JPEG_* word of its failed interval with the lowest row number in desc, or
+ *            SF_JPEG_BAD_DESC where the clean intervals do not cover the image's MCUs.  (A row whose `image` is out of range is
+ *            reported at the nearest image.)  A failed image leaves unspecified pixels inside its own slot; the other images of the
+ *            batch are not affected.
+ *   The arithmetic, all integer (>> arithmetic); tests/jpeg_decode_cases.py restates it, and on every file of tests/golden/jpeg_decode
+ *   that restatement, this entry point and libjpeg-turbo (through PIL) agree bit for bit:
+ *   Entropy decoding.  T.81 F.2.2: canonical codes from BITS / HUFFVAL (Annex C), MSB first; a DC difference of category s <= 11 on top
+ *     of the component's prediction, which starts at 0 in every interval; AC symbols run << 4 | size along the zigzag scan with size
+ *     <= 10, ZRL (F0) and EOB (00).  Coefficient k of component c is multiplied by the c's step k and stored as int16 in natural
+ *     order.  Bounds: every dequantised coefficient has |c| <= 2048 and the 64 of a block sum |c| <= 18432, else
+ *     SF_JPEG_COEF_RANGE.  No file made from 8-bit samples gets there: the exact DCT of samples - 128 has |F| <= 1024 and sum |F| <=
+ *     8 ||s||_2 <= 8192, a quantiser that rounds to the nearest level or towards zero gives 0 or at most |F| + q / 2 <= 2 |F|, q <=
+ *     255.  The per-coefficient bound X = 2048 alone does NOT keep the inverse DCT inside 32 bits (64 coefficients of 2048 with the
+ *     signs of one sample's basis reach 1.74 x 2^31 in the second pass); with both bounds no intermediate of either pass passes
+ *     0.88 x 2^31 (csrc/jpeg_decode_core.h has the derivation, tests/jpeg_decode_cases.idct_bounds() recomputes it from the
+ *     data flow of the transform, not from samples).
+ *   Inverse DCT.  libjpeg's jidctint.c "islow" exactly, in 32-bit integers, CONST_BITS = 13, PASS1_BITS = 2, the constants 2446 3196
+ *     4433 6270 7373 9633 12299 15137 16069 16819 20995 25172 = FIX(0.298631336) .. FIX(3.072711026).  One pass on in[0 .. 7]:
+ *       even: z1 = (in2 + in6) 4433, tmp2 = z1 - in6 15137, tmp3 = z1 + in2 6270, tmp0 = (in0 + in4) << 13, tmp1 = (in0 - in4) << 13,
+ *             tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2
+ *       odd:  t0 = in7, t1 = in5, t2 = in3, t3 = in1; z1 = t0 + t3, z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3, z5 = (z3 + z4) 9633;
+ *             t0 *= 2446, t1 *= 16819, t2 *= 25172, t3 *= 12299; z1 *= -7373, z2 *= -20995, z3 = z3 (-16069) + z5, z4 = z4 (-3196) + z5;
+ *             t0 += z1 + z3, t1 += z2 + z4, t2 += z2 + z3, t3 += z1 + z4
+ *       out0 / out7 = tmp10 +- t3, out1 / out6 = tmp11 +- t2, out2 / out5 = tmp12 +- t1, out3 / out4 = tmp13 +- t0.
+ *     Columns first, descaled (x + 1024) >> 11; then rows, descaled (x + 2^17) >> 18, + 128, clamped to 0 .. 255.
+ *   Chroma upsampling.  libjpeg's "fancy" triangle filters on the cw = ceil(w / hs) x ch = ceil(h / vs) real samples of a chroma plane
+ *     (the block padding is never read).  2 x 1: output 2 i = (3 c[i] + c[i - 1] + 1) >> 2, output 2 i + 1 = (3 c[i] + c[i + 1] + 2) >> 2,
+ *     output 0 = c[0], output 2 cw - 1 = c[cw - 1].  2 x 2: for output row y the chroma row r = y / 2 and its nearer neighbour n = r - 1
+ *     (y even) or r + 1 (y odd), clamped to 0 .. ch - 1; t[i] = 3 c[r][i] + c[n][i]; output 2 i = (3 t[i] + t[i - 1] + 8) >> 4, output
+ *     2 i + 1 = (3 t[i] + t[i + 1] + 7) >> 4, output 0 = (4 t[0] + 8) >> 4, output 2 cw - 1 = (4 t[cw - 1] + 7) >> 4.
+ *     As in libjpeg (jinit_upsampler), a plane of cw <= 2 samples (w <= 4) is too narrow for the filters: its samples are replicated
+ *     instead, out[y][x] = c[y / vs][x / 2].
+ *   Colour.  Cb' = Cb - 128, Cr' = Cr - 128: R = Y + ((91881 Cr' + 32768) >> 16), G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16),
+ *     B = Y + ((116130 Cb' + 32768) >> 16), each clamped to 0 .. 255.
+ *   Safety.  For ANY bytes in data, desc and tables every read of `data` stays inside the interval's [in_off, in_off + in_len), every
+ *     write of the entropy stage inside the workspace blocks of the interval's own MCUs, and an interval ends within 8 in_len symbol
+ *     decodes + in_len refill steps + min(6 n_mcus, 8 in_len + 1) block stores (csrc/jpeg_decode_core.h argues both; the same core
+ *     runs under the host sanitizers as csrc/host/jpeg_decode_host_main.cpp).  Two runs are bitwise equal.
+ * sf_jpeg_decode_ws_bytes: the workspace (int16 coefficients [image][component][block row][block column][64], the components' uint8
+ *   planes padded to whole blocks, two words per image); -1 for a refused shape or n_images.
+ * One memset (the two words per image) and four launches (entropy: one wave per interval; status: a thread per image; inverse DCT: a
+ *   thread per block; upsampling and colour: a thread per pixel); dependencies between workgroups are launch boundaries: no flags, no
+ *   spinning, no host synchronisation.
+ *   SF_ERR_BAD_ARG before anything is enqueued for: null pointers, data_bytes < 0, n_intervals outside 1 .. 2^26, n_table_sets or
+ *   n_images outside 1 .. 65535, h or w < 1, components outside {1, 3}, a sampling outside the list above, out_channels outside {1, 3}
+ *   or 1 with 3 components, out_row_stride < w out_channels, out_image_stride < (h - 1) out_row_stride + w out_channels, desc not
+ *   8-byte, status not 4-byte or ws not 16-byte aligned, ws_bytes too small.  SF_ERR_UNSUPPORTED for h or w above SF_JPEG_MAX_DIM
+ *   (checked after the sampling and channel checks).  What desc and tables hold is checked on the device. */
+#define SF_JPEG_DESC_WORDS 6
+#define SF_JPEG_TABLE_SET_BYTES 1824
+enum {
+    SF_JPEG_OK = 0,
+    SF_JPEG_BAD_CODE = 1,      /* bits that are no code of the table */
+    SF_JPEG_BAD_RUN = 2,       /* a run past coefficient 63, a ZRL with no coefficient left to follow it, a run / size symbol baseline lacks */
+    SF_JPEG_BAD_CATEGORY = 3,  /* DC category above 11 or AC category above 10 */
+    SF_JPEG_TRUNCATED = 4,     /* the interval's input ends inside an MCU */
+    SF_JPEG_NOT_CONSUMED = 5,  /* behind the last MCU more than 7 bits remain, or the remaining bits are not all 1 */
+    SF_JPEG_BAD_DESC = 6,      /* a descriptor outside the buffers, images, MCUs or table sets; intervals that do not cover the image */
+    SF_JPEG_COEF_RANGE = 7,    /* a dequantised coefficient beyond 2048, or a block whose absolute values sum beyond 18432 */
+    SF_JPEG_BAD_TABLE = 8,     /* a Huffman specification with more than 256 codes, or more codes of a length than it has patterns */
+    SF_JPEG_BAD_MARKER = 9     /* an FF byte inside an interval that is not followed by 00 */
+};
+int64_t sf_jpeg_decode_ws_bytes(int n_images, int h, int w, int components, int hs, int vs);
+int sf_jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* desc, int n_intervals, const uint8_t* tables, int n_table_sets,
+                   int n_images, int h, int w, int components, int hs, int vs, uint8_t* out, int64_t out_image_stride,
+                   int64_t out_row_stride, int out_channels, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- Spring .flo5 output: the HDF5 filters shuffle -> deflate of a batch of flow fields, chunk by chunk (flo5.flo5_file frames them) ---
  * sf_flo5_encode: field i is two planes, element (ch, y, x) at flow + i field_stride + ch ch_stride + y row_stride + x (strides in

@@ -202,6 +202,8 @@ SIGNATURES = {
     "sf_jpeg_encode_bound": (_i64, [_i, _i, _i]),
     "sf_jpeg_encode_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "sf_jpeg_encode": (_i, [_vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sf_jpeg_decode_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
+    "sf_jpeg_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp, _vp, _i64, _vp]),
     "sf_flo5_chunk_bound": (_i64, [_i, _i]),
     "sf_flo5_encode_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "sf_flo5_encode": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
@@ -232,7 +234,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 134:
+    if lib.sf_version() < 135:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -9,6 +9,9 @@ jpeg_gpu.encode_batch makes on the GPU go in as they are.  The layout:
 
 Frames stream to disk as they come; the sizes and counts are patched on close().  Files stay below 2^31 - 1 bytes (OpenDML
 extensions are not written).  MJPEG decoders assume the Annex K.3 Huffman tables and YCbCr; the frames carry their own DHT anyway.
+
+MjpegReader is the way back: it finds the frames of such a file (this writer's or another's: with or without `idx1`, `rec ` lists,
+`##db` chunks, empty chunks for repeated frames) and hands their bytes to jpeg_gpu.decode_batch.
 """
 from __future__ import annotations
 
@@ -107,3 +110,169 @@ class MjpegWriter:
 
 def _chunk(tag: bytes, payload: bytes) -> bytes:
     return tag + struct.pack("<I", len(payload)) + payload + b"\x00" * (len(payload) & 1)
+
+
+class MjpegReader:
+    """The frames of a Motion-JPEG AVI file as a lazy sequence: `fps` (dwRate / dwScale of the video stream), `hw`, len(),
+    `frame_bytes(i)` (the JPEG file of frame i), `device_batch(lo, hi, dev)` (frames lo .. hi - 1 decoded on the GPU by
+    jpeg_gpu.decode_batch: uint8 [hi - lo, H, W, 3] where predict_video reads them) and reader[i] (one frame decoded on the GPU,
+    returned as a host array).  The frames come from `idx1` where the file has one, else from a walk of `movi` (`rec ` lists
+    included); `##dc` and `##db` chunks of the first video stream count, a chunk of length 0 repeats the frame before it.
+    ValueError for a file that is no AVI, whose video stream is not MJPG, or that continues in OpenDML `AVIX` segments.  Frames of
+    two interlaced fields (`AVI1`) and audio streams are not handled."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self.f = open(path, "rb")
+        try:
+            self._index()
+        except Exception:
+            self.f.close()
+            raise
+
+    def _bad(self, msg: str) -> ValueError:
+        return ValueError(f"{self.path}: {msg}")
+
+    def _chunks(self, start: int, end: int):
+        """(tag, payload offset, payload size) of the chunks in [start, end); a chunk that crosses `end` stops the walk."""
+        at = start
+        while at + 8 <= end:
+            self.f.seek(at)
+            tag, size = struct.unpack("<4sI", self.f.read(8))
+            if at + 8 + size > end:
+                raise self._bad(f"chunk {tag!r} at {at}: {size} bytes cross the end of its list at {end}")
+            yield tag, at + 8, size
+            at += 8 + size + (size & 1)
+
+    def _index(self) -> None:
+        self.f.seek(0, 2)
+        total = self.f.tell()
+        self.f.seek(0)
+        head = self.f.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+            raise self._bad("not an AVI file (no RIFF 'AVI ' header)")
+        end = min(total, 8 + struct.unpack("<I", head[4:8])[0])
+        if total >= end + 12:
+            self.f.seek(end + (end & 1))
+            more = self.f.read(12)
+            if more[:4] == b"RIFF" and more[8:12] == b"AVIX":
+                raise self._bad("OpenDML file (AVIX segments) -- only AVI 1.0 files are read")
+        stream, movi, idx1, streams = None, None, None, 0
+        self.fps, self.hw = None, None
+        for tag, at, size in self._chunks(12, end):
+            if tag == b"LIST":
+                self.f.seek(at)
+                kind = self.f.read(4)
+                if kind == b"hdrl":
+                    for t2, a2, s2 in self._chunks(at + 4, at + size):
+                        if t2 != b"LIST":
+                            continue
+                        self.f.seek(a2)
+                        if self.f.read(4) != b"strl":
+                            continue
+                        strh = strf = None
+                        for t3, a3, s3 in self._chunks(a2 + 4, a2 + s2):
+                            self.f.seek(a3)
+                            if t3 == b"strh":
+                                strh = self.f.read(s3)
+                            elif t3 == b"strf":
+                                strf = self.f.read(s3)
+                        if strh is not None and len(strh) >= 28 and strh[:4] == b"vids" and stream is None:
+                            if strf is None or len(strf) < 20:
+                                raise self._bad("video stream without a format chunk")
+                            codec = strf[16:20]
+                            if codec.upper() != b"MJPG":
+                                raise self._bad(f"video stream is {codec!r} / {strh[4:8]!r}, not MJPG")
+                            scale, rate = struct.unpack_from("<II", strh, 20)
+                            if scale == 0 or rate == 0:
+                                raise self._bad(f"video stream with rate {rate} / scale {scale}")
+                            w, h = struct.unpack_from("<ii", strf, 4)
+                            stream, self.fps, self.hw = streams, rate / scale, (abs(h), abs(w))
+                        streams += 1
+                elif kind == b"movi":
+                    movi = (at, size)
+            elif tag == b"idx1":
+                idx1 = (at, size)
+        if stream is None:
+            raise self._bad("no video stream")
+        if movi is None:
+            raise self._bad("no movi list")
+        tags = (b"%02ddc" % stream, b"%02ddb" % stream)
+        entries = []                                                    # (payload offset, size), 0 for a repeated frame
+        if idx1 is not None and idx1[1] >= 16:
+            self.f.seek(idx1[0])
+            raw = self.f.read(idx1[1] - idx1[1] % 16)
+            rows = [struct.unpack_from("<4sIII", raw, k) for k in range(0, len(raw), 16)]
+            rows = [(off, size) for tag, _, off, size in rows if tag in tags]
+            if rows:
+                # offsets count from the 'movi' tag or from the start of the file: whichever finds the first frame's chunk header
+                for base in (movi[0], 0):
+                    self.f.seek(base + rows[0][0])
+                    if self.f.read(4) in tags:
+                        break
+                else:
+                    raise self._bad("idx1 does not point at the frames")
+                entries = [(base + off + 8, size) for off, size in rows]
+                if any(at + size > total for at, size in entries):
+                    raise self._bad("idx1 points past the end of the file")
+        if not entries:
+            def walk(start, stop):
+                for tag, at, size in self._chunks(start, stop):
+                    if tag == b"LIST":
+                        self.f.seek(at)
+                        if self.f.read(4) == b"rec ":
+                            walk(at + 4, at + size)
+                    elif tag in tags:
+                        entries.append((at, size))
+            walk(movi[0] + 4, movi[0] + movi[1])
+        self.frames = []
+        for at, size in entries:
+            if size == 0:
+                if not self.frames:
+                    raise self._bad("the first frame is empty")
+                self.frames.append(self.frames[-1])
+            else:
+                self.frames.append((at, size))
+        if not self.frames:
+            raise self._bad("no frames")
+        if self.hw[0] == 0 or self.hw[1] == 0:
+            w, h = jpeg_size(self.frame_bytes(0))
+            self.hw = (h, w)
+
+    def __len__(self) -> int:
+        return len(self.frames)
+
+    def frame_bytes(self, i: int) -> bytes:
+        at, size = self.frames[i]
+        self.f.seek(at)
+        data = self.f.read(size)
+        if len(data) != size:
+            raise self._bad(f"frame {i} crosses the end of the file")
+        return data
+
+    def device_batch(self, lo: int, hi: int, dev):
+        """The frames lo .. hi - 1 as uint8 [hi - lo, H, W, 3] on `dev`; raises without a GPU (there is no host decoder)."""
+        from . import jpeg_gpu
+        out = jpeg_gpu.decode_batch([self.frame_bytes(i) for i in range(lo, hi)], dev, names=[f"{self.path}: frame {i}" for i in range(lo, hi)])
+        if tuple(out.shape[1:3]) != self.hw:
+            raise self._bad(f"frame {lo} is {tuple(out.shape[1:3])}, the stream header says {self.hw}")
+        return out
+
+    def __getitem__(self, i: int):
+        if isinstance(i, slice):
+            raise TypeError("MjpegReader is indexed by frame number")
+        import torch
+        i = range(len(self.frames))[i]
+        return self.device_batch(i, i + 1, torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu")[0].cpu().numpy()
+
+    def close(self) -> None:
+        if self.f is not None:
+            self.f.close()
+            self.f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -160,7 +160,8 @@ def vis_flow_video(flows_result: Sequence[torch.Tensor], save_path: str = "flow_
 def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, clips_per_step: int = 8, mode: str = "sintel",
                                   save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host",
                                   png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90) -> int:
-    """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames: video.FrameDir ->
+    """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
+    baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
     are coloured on the GPU and written as ``save_dir/frame_%04d.png`` (numbered by pair) and, with `flo_dir`, as Middlebury
     ``flo_dir/frame_%04d.flo``.  png_decode="gpu": the frames' PNG rows are unfiltered on the GPU (video.FrameDir(decode="gpu")), the
@@ -172,7 +173,7 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
     _check_png_encode(png_encode)
-    frames = video.FrameDir(path, decode=png_decode)
+    frames = video.open_frames(path, png_decode)
     if not torch.cuda.is_available():
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -211,9 +212,9 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m streamflow_amd.demo",
-                                 description="Flow fields of a directory of PNG frames, as colour-wheel PNGs, a Motion-JPEG AVI "
+                                 description="Flow fields of a directory of PNG or JPEG frames or a Motion-JPEG AVI file, as colour-wheel PNGs, a Motion-JPEG AVI "
                                              "video and .flo files")
-    ap.add_argument("--frames", required=True, help="directory of PNG frames (sorted by name)")
+    ap.add_argument("--frames", required=True, help="directory of PNG frames or of baseline JPEG frames (sorted by name), or a Motion-JPEG .avi file")
     ap.add_argument("--ckpt", required=True, help="StreamFlow checkpoint")
     ap.add_argument("--out", default=None, help="directory for frame_%%04d.png (may be left out only with --video)")
     ap.add_argument("--video", default=None, help="one Motion-JPEG AVI file of the colour-wheel images, encoded on the GPU")

@@ -1525,6 +1525,47 @@ def jpeg_encode(images: torch.Tensor, qtables):
     return segments, lengths
 
 
+JPEG_DESC_WORDS, JPEG_TABLE_SET_BYTES = 6, 1824
+
+
+@on_tensor_device
+def jpeg_decode(data: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, n_images: int, h: int, w: int, components: int, hs: int,
+                vs: int, out_channels: int = 3):
+    """Baseline JPEG files of one geometry -> pixels (sf_jpeg_decode, csrc/jpeg_decode.hip: Huffman decoding a wave per restart
+    interval, libjpeg's integer inverse DCT, fancy chroma upsampling, YCbCr -> RGB; the host half is jpeg_gpu.parse / pack).  data
+    uint8 [B]: the entropy-coded bytes, still stuffed; desc int64 [n_intervals, 6] = (in_off, in_len, image, first_mcu, n_mcus,
+    table_set) per restart interval; tables uint8 [n_sets, 1824]; all three on the same GPU.  components 1 or 3, hs x vs the luma
+    sampling (1 x 1, 2 x 1, 2 x 2).  Returns (images uint8 [n_images, h, w, out_channels], status int32 [n_images]) on that GPU:
+    status 0, or an index into jpeg_gpu.DECODE_STATUS (include/streamflow_hip.h SF_JPEG_*) for an image whose pixels are then
+    unspecified.  Enqueued on the current stream, no synchronisation: reading the status is the caller's."""
+    for name, t, dt in (("data", data, torch.uint8), ("desc", desc, torch.int64), ("tables", tables, torch.uint8)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"jpeg_decode: {name} must be on the GPU (got {getattr(t, 'device', type(t).__name__)}); "
+                               "there is no CPU fallback")
+        if t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"jpeg_decode: {name} must be a contiguous {dt} tensor, got {t.dtype} {tuple(t.shape)}")
+    if data.dim() != 1 or desc.dim() != 2 or desc.shape[1] != JPEG_DESC_WORDS or desc.shape[0] < 1 or tables.dim() != 2 or \
+            tables.shape[1] != JPEG_TABLE_SET_BYTES or tables.shape[0] < 1:
+        raise RuntimeError(f"jpeg_decode: expected data [B], desc [n >= 1, {JPEG_DESC_WORDS}], tables [s >= 1, {JPEG_TABLE_SET_BYTES}]; "
+                           f"got {tuple(data.shape)}, {tuple(desc.shape)}, {tuple(tables.shape)}")
+    if data.device != desc.device or data.device != tables.device:
+        raise RuntimeError(f"jpeg_decode: data, desc and tables must share a device ({data.device}, {desc.device}, {tables.device})")
+    n, h, w, c, hs, vs, oc = (int(v) for v in (n_images, h, w, components, hs, vs, out_channels))
+    lib = _lib.load()
+    ws_bytes = lib.sf_jpeg_decode_ws_bytes(n, h, w, c, hs, vs)
+    if ws_bytes < 0 or oc not in (1, 3):
+        raise RuntimeError(f"jpeg_decode: n = {n}, h = {h}, w = {w}, components = {c}, sampling {hs} x {vs}, out_channels = {oc} is "
+                           "outside what sf_jpeg_decode takes")
+    out = torch.empty(n, h, w, oc, dtype=torch.uint8, device=data.device)
+    status = torch.empty(n, dtype=torch.int32, device=data.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=data.device)
+    # an empty tensor has no storage to point at: any non-null, never dereferenced address stands for it
+    _lib.check(lib.sf_jpeg_decode(data.data_ptr() or status.data_ptr(), data.numel(), desc.data_ptr(), int(desc.shape[0]), tables.data_ptr(),
+                                  int(tables.shape[0]), n, h, w, c, hs, vs, out.data_ptr(), h * w * oc, w * oc, oc, status.data_ptr(),
+                                  ws.data_ptr(), ws_bytes, _lib.stream()), "sf_jpeg_decode")
+    return out, status
+
+
 @on_tensor_device
 def flow_to_kitti16(flows: torch.Tensor) -> torch.Tensor:
     """KITTI flow codes of device flows (sf_flow_to_kitti16; flow_io.kitti_encode for float32): flows fp32 [N, 2, H, W] -> torch.uint16

@@ -113,6 +113,76 @@ class FrameDir:
         return out
 
 
+def _jpeg_size(path: str) -> Tuple[int, int]:
+    from .avi import jpeg_size
+    with open(path, "rb") as f:
+        head = f.read(65536)
+        try:
+            w, h = jpeg_size(head)
+        except ValueError:
+            try:
+                w, h = jpeg_size(head + f.read())                        # a long APPn segment (a thumbnail, a profile) before the frame header
+            except ValueError as e:
+                raise IOError(f"{path}: {e}") from None
+    return h, w
+
+
+JPEG_PATTERNS = ("*.jpg", "*.jpeg", "*.JPG", "*.JPEG")
+
+
+class JpegDir:
+    """The baseline JPEG frames of a directory (`pattern`, default *.jpg and *.jpeg), sorted by name, as a lazy sequence.  They are
+    decoded on the GPU only (jpeg_gpu.decode_batch: one sf_jpeg_decode call per batch): predict_video takes a batch's frames through
+    `device_batch`, and frames[i] decodes one frame on the current GPU and returns the host array uint8 [H, W, 3] (grey replicated
+    to three channels).  All frames must have one size: the frame headers are compared when the object is made."""
+
+    def __init__(self, path: str, pattern: Optional[str] = None):
+        patterns = JPEG_PATTERNS if pattern is None else (pattern,)
+        self.paths = sorted({p for pat in patterns for p in glob.glob(os.path.join(path, pat))})
+        if not self.paths:
+            raise FileNotFoundError(f"no frames matching {' / '.join(patterns)} in {path}")
+        self.hw = _jpeg_size(self.paths[0])
+        for p in self.paths[1:]:
+            if _jpeg_size(p) != self.hw:
+                raise ValueError(f"{p}: frame size {_jpeg_size(p)} differs from {self.hw} of {self.paths[0]}")
+
+    def __len__(self) -> int:
+        return len(self.paths)
+
+    def device_batch(self, lo: int, hi: int, dev: torch.device) -> torch.Tensor:
+        """The frames lo .. hi - 1 as uint8 [hi - lo, H, W, 3] on `dev`; raises without a GPU (there is no host decoder)."""
+        from . import jpeg_gpu
+        out = jpeg_gpu.decode_batch(self.paths[lo:hi], dev)
+        if tuple(out.shape[1:3]) != self.hw:
+            raise ValueError(f"{self.paths[lo]}: frame size {tuple(out.shape[1:3])} differs from {self.hw}")
+        return out
+
+    def __getitem__(self, i: int) -> np.ndarray:
+        if isinstance(i, slice):
+            raise TypeError("JpegDir is indexed by frame number")
+        i = range(len(self.paths))[i]
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        return self.device_batch(i, i + 1, dev)[0].cpu().numpy()
+
+
+def open_frames(path: str, png_decode: str = "host"):
+    """The frame source behind a path: a FrameDir for a directory of .png files (png_decode: its `decode`), a JpegDir for a directory
+    of .jpg / .jpeg files, an avi.MjpegReader for a file.  A directory that holds both kinds is a ValueError, one that holds neither
+    and a path that does not exist a FileNotFoundError."""
+    if os.path.isdir(path):
+        png = glob.glob(os.path.join(path, "*.png"))
+        jpg = [p for pat in JPEG_PATTERNS for p in glob.glob(os.path.join(path, pat))]
+        if png and jpg:
+            raise ValueError(f"{path} holds {len(png)} .png and {len(jpg)} .jpg / .jpeg frames: one kind per directory")
+        if jpg:
+            return JpegDir(path)
+        return FrameDir(path, decode=png_decode)                         # raises FileNotFoundError for a directory without frames
+    if os.path.isfile(path):
+        from .avi import MjpegReader
+        return MjpegReader(path)
+    raise FileNotFoundError(f"{path}: neither a directory of frames nor a video file")
+
+
 class _Source:
     """The frames argument of predict_video behind one face: n, (H, W), and `device_frames(lo, hi, dev)` -> (uint8 device tensor,
     channels_last, number of its first frame).  Everything is checked that can be without touching the GPU or decoding a frame."""
