@@ -1052,6 +1052,70 @@ int sf_jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* desc,
                    int n_images, int h, int w, int components, int hs, int vs, uint8_t* out, int64_t out_image_stride,
                    int64_t out_row_stride, int out_channels, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
 
+/* sf_jpeg_decode_split: sf_jpeg_decode with LONG intervals decoded in parallel.  sf_jpeg_decode gives every restart interval one wave,
+ *   and a file without DRI -- what PIL, ffmpeg's default, cameras and capture cards write -- is one interval.  Here an interval with
+ *   in_len >= split_min_bytes takes the split route: a thread per segment of segment_bytes bytes of its UNSTUFFED stream, by the
+ *   self-synchronising method of Klein and Wiseman as Weissenberger and Schmidt applied it to JPEG.  The other intervals take
+ *   sf_jpeg_decode's wave route.  split_min_bytes = 0 splits every interval; a value above data_bytes makes the call sf_jpeg_decode's
+ *   (the same launches).  All arguments up to `status` are sf_jpeg_decode's; segment_bytes is a power of two in 8 .. 4096.
+ *   The unstuffed stream.  The interval's bytes without the 00 of every FF 00, up to the first FF that is the interval's last byte or
+ *     has another byte than 00 behind it: the usable stream ends there, and running out of bits is then SF_JPEG_BAD_MARKER instead of
+ *     SF_JPEG_TRUNCATED.  Segment s is bits [8 s segment_bytes, 8 min((s + 1) segment_bytes, length)) of it; an empty stream has one
+ *     (empty) segment.
+ *   A state is (bit, slot, k): the offset of the next symbol's first bit in the unstuffed stream, the block slot inside the MCU (the hs vs
+ *     luma blocks, then Cb, then Cr; grey: slot 0 only) and the zigzag index of the next coefficient, k = 0: the next symbol is a DC
+ *     symbol.  A step decodes one symbol with the checks of sf_jpeg_decode's entropy decoding, in their order.  A walk of a segment
+ *     goes from a state to the first symbol boundary at or behind the segment's last bit, or stops in front of a symbol the stream has
+ *     no bits left for.
+ *   The lenient rule.  The walks that only look for the boundaries store nothing, and ANY error (no code, a run past 63, a category
+ *     baseline lacks) ends the current block ONE BIT behind the failed symbol's first bit; decoding goes on with the next slot's DC
+ *     symbol.  A speculative chain therefore never dies (a dead one would let the truth advance one segment per round only), and from
+ *     a true state on a valid stream the walk takes exactly the strict steps.  It counts the blocks it ends.
+ *   The rounds.  Every segment is first walked from (its first bit, 0, 0).  Then, per window of 256 segments in stream order: the window's
+ *     first segment enters with the previous window's final exit, the interval's first with (0, 0, 0); each round sets segment k's entry to
+ *     segment k - 1's exit of the round before, and the segments whose entry changed walk again; until a round changes nothing, which is
+ *     at most the window's segment count, by induction from its first segment.  The fixed point is the serial decoder's states; a
+ *     prefix sum of the block counts gives every segment the ordinal of the block its entry lies in.
+ *   The strict walk.  From its true entry every segment decodes for real: AC coefficients dequantised into their blocks, the RAW DC
+ *     difference into coefficient 0, and only while the block's ordinal is below n_mcus x blocks per MCU -- for ANY input every write
+ *     stays inside the interval's own MCUs.  The walk that ends the last block makes sf_jpeg_decode's closing check (at most 7 bits left,
+ *     all 1; SF_JPEG_BAD_MARKER where the stream ends at a marker); the last segment's walk reports SF_JPEG_TRUNCATED / BAD_MARKER where
+ *     the stream ends in front of the last block.  Then, per component in scan order, 64-bit prefix sums of the DC differences give the
+ *     predictions: |pred| <= 2048 and |pred q| <= 2048 as in sf_jpeg_decode, the dequantised DC into coefficient 0, and the block's
+ *     sum |c| <= 18432.
+ *   Status of a split interval: every error has the key (ordinal of its block in the interval) << 6 | phase << 4 | word -- phase 0 the DC
+ *     range checks, 1 an entropy error (an AC coefficient beyond 2048 included), 2 the block's sum; the closing check has the
+ *     interval's block count as its ordinal, a Huffman specification that is none key SF_JPEG_BAD_TABLE alone -- and the interval's word
+ *     is that of the SMALLEST key: the first error in stream order, the only one that means anything, since the segments behind it hold
+ *     garbage by construction.  It enters the image's status exactly as a wave's word does.
+ *   Contract.  An image's status is 0 exactly when sf_jpeg_decode's is, and then its pixels are bitwise sf_jpeg_decode's.  A nonzero word
+ *     is the split route's own: sf_jpeg_decode's depends on how far its bit buffer had read ahead (a marker behind the last MCU), which is
+ *     not reproduced.  Two runs are bitwise equal.
+ *   Launches.  sf_jpeg_decode's memset and four launches, plus -- unless split_min_bytes > data_bytes -- three memsets (the coefficient
+ *     area, since two segments may each write their own coefficients of one block; the workgroup map; the keys) and seven launches in
+ *     front of the wave launch, which skips the split intervals: plan (one workgroup scans desc on the device: which intervals split,
+ *     their first workgroup of 256 segment slots and their share of the unstuffed area, by exclusive scans; the host never reads desc
+ *     and sizes grids and areas from the bounds data_bytes / (256 segment_bytes) + n_intervals workgroups and data_bytes + 16 n_intervals
+ *     bytes, which intervals that do not overlap always fit -- one that does not fit takes the wave route), unstuff (a workgroup per
+ *     split interval: count per chunk, scan, copy), the speculative walks (a thread per segment), the rounds (a workgroup per split
+ *     interval), the strict walks (a thread per segment), the DC sums (a workgroup per split interval and component), the interval
+ *     words.  Dependencies between workgroups are launch boundaries: no flags, no spinning, no host synchronisation.
+ *   Safety.  For ANY bytes in data, desc and tables: `data` is read inside an interval's [in_off, in_off + in_len) only, every write of
+ *     the entropy stage stays inside the workspace and, for coefficients, inside the blocks of the interval's own MCUs; every walk
+ *     consumes at least one bit per step and ends within 8 segment_bytes + 27 bits, and a window's rounds are at most its segments + 1
+ *     (csrc/jpeg_sync_core.h and csrc/jpeg_decode.hip argue both; the same functions run under the host sanitizers as
+ *     csrc/host/jpeg_sync_host_main.cpp).
+ * sf_jpeg_decode_split_ws_bytes: sf_jpeg_decode_ws_bytes plus the split route's areas; -1 for what sf_jpeg_decode_ws_bytes refuses,
+ *   data_bytes outside 0 .. 2^40, n_intervals outside 1 .. 2^26, a segment_bytes outside its set, or 2^31 workgroups and more.
+ *   SF_ERR_BAD_ARG before anything is enqueued for sf_jpeg_decode's list, segment_bytes outside its set, split_min_bytes < 0 and
+ *   ws_bytes too small; SF_ERR_UNSUPPORTED as there. */
+int64_t sf_jpeg_decode_split_ws_bytes(int n_images, int h, int w, int components, int hs, int vs, int64_t data_bytes, int n_intervals,
+                                      int segment_bytes);
+int sf_jpeg_decode_split(const uint8_t* data, int64_t data_bytes, const int64_t* desc, int n_intervals, const uint8_t* tables,
+                         int n_table_sets, int n_images, int h, int w, int components, int hs, int vs, uint8_t* out,
+                         int64_t out_image_stride, int64_t out_row_stride, int out_channels, int32_t* status, int segment_bytes,
+                         int64_t split_min_bytes, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- Spring .flo5 output: the HDF5 filters shuffle -> deflate of a batch of flow fields, chunk by chunk (flo5.flo5_file frames them) ---
  * sf_flo5_encode: field i is two planes, element (ch, y, x) at flow + i field_stride + ch ch_stride + y row_stride + x (strides in
  *   floats; an unpadded view of a padded field goes in as it is).  The HDF5 dataset is float32 [h][w][2] in chunks of

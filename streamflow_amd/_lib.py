@@ -204,6 +204,8 @@ SIGNATURES = {
     "sf_jpeg_encode": (_i, [_vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "sf_jpeg_decode_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
     "sf_jpeg_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp, _vp, _i64, _vp]),
+    "sf_jpeg_decode_split_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i64, _i, _i]),
+    "sf_jpeg_decode_split": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp, _i, _i64, _vp, _i64, _vp]),
     "sf_flo5_chunk_bound": (_i64, [_i, _i]),
     "sf_flo5_encode_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "sf_flo5_encode": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),

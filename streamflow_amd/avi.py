@@ -119,10 +119,14 @@ class MjpegReader:
     returned as a host array).  The frames come from `idx1` where the file has one, else from a walk of `movi` (`rec ` lists
     included); `##dc` and `##db` chunks of the first video stream count, a chunk of length 0 repeats the frame before it.
     ValueError for a file that is no AVI, whose video stream is not MJPG, or that continues in OpenDML `AVIX` segments.  Frames of
-    two interlaced fields (`AVI1`) and audio streams are not handled."""
+    two interlaced fields (`AVI1`) and audio streams are not handled.  `split` is jpeg_gpu.decode_batch's: how frames without restart
+    markers -- what most encoders write -- are decoded in parallel."""
 
-    def __init__(self, path: str):
-        self.path = path
+    def __init__(self, path: str, split: str = "auto"):
+        from .jpeg_gpu import SPLIT_MODES
+        if split not in SPLIT_MODES:
+            raise ValueError(f"MjpegReader: split = {split!r} (one of {', '.join(SPLIT_MODES)})")
+        self.path, self.split = path, split
         self.f = open(path, "rb")
         try:
             self._index()
@@ -253,7 +257,8 @@ class MjpegReader:
     def device_batch(self, lo: int, hi: int, dev):
         """The frames lo .. hi - 1 as uint8 [hi - lo, H, W, 3] on `dev`; raises without a GPU (there is no host decoder)."""
         from . import jpeg_gpu
-        out = jpeg_gpu.decode_batch([self.frame_bytes(i) for i in range(lo, hi)], dev, names=[f"{self.path}: frame {i}" for i in range(lo, hi)])
+        out = jpeg_gpu.decode_batch([self.frame_bytes(i) for i in range(lo, hi)], dev, names=[f"{self.path}: frame {i}" for i in range(lo, hi)],
+                                    split=self.split)
         if tuple(out.shape[1:3]) != self.hw:
             raise self._bad(f"frame {lo} is {tuple(out.shape[1:3])}, the stream header says {self.hw}")
         return out

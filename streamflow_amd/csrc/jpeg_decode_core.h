@@ -262,9 +262,10 @@ SF_JPEGDEC_FN int build_tables(P& p, Tables& t, const uint8_t* set, int nc) {
     return st;
 }
 
-// One symbol.  >= 0: the symbol; < 0: -status.
-template <class P>
-SF_JPEGDEC_FN int decode_symbol(P& p, Bits<P>& b, const Huff& t) {
+// One symbol.  >= 0: the symbol; < 0: -status.  B is a bit reader with Bits' members buf, cnt, refill() and failure(): Bits itself, or
+// the flat reader of csrc/jpeg_sync_core.h.
+template <class P, class B>
+SF_JPEGDEC_FN int decode_symbol(P& p, B& b, const Huff& t) {
     if (b.cnt < 16) b.refill();
     const uint32_t look = (uint32_t)(b.buf >> 48);                          // bits past cnt are zero
     const uint32_t e = p.uni(t.fast[look >> (16 - kFastBits)]);
@@ -285,8 +286,8 @@ SF_JPEGDEC_FN int decode_symbol(P& p, Bits<P>& b, const Huff& t) {
 }
 
 // `s` more bits as a signed value of category s (T.81 F.2.2.1 EXTEND), 1 <= s <= 11.
-template <class P>
-SF_JPEGDEC_FN bool receive(Bits<P>& b, int s, int& v) {
+template <class B>
+SF_JPEGDEC_FN bool receive(B& b, int s, int& v) {
     uint32_t raw;
     if (!b.take(s, raw)) return false;
     v = (int)raw < (1 << (s - 1)) ? (int)raw - (1 << s) + 1 : (int)raw;

@@ -159,7 +159,8 @@ def vis_flow_video(flows_result: Sequence[torch.Tensor], save_path: str = "flow_
 
 def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, clips_per_step: int = 8, mode: str = "sintel",
                                   save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host",
-                                  png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90) -> int:
+                                  png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90,
+                                  jpeg_split: str = "auto") -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
     baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
@@ -168,12 +169,13 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     same bytes as the host decoder's.  png_encode="gpu": the colour images are filtered and deflated on the GPU
     (png_gpu.encode_batch: no uncompressed image crosses to the host; the same pixels, other file bytes).  With `video_path` every
     batch's images are also encoded as JPEG frames on the GPU (IJG quality `jpeg_quality`) and appended to one Motion-JPEG AVI file
-    of `fps` frames per second (avi.MjpegWriter).  Runs on the current GPU.  Returns the number of pairs."""
+    of `fps` frames per second (avi.MjpegWriter).  jpeg_split: jpeg_gpu.decode_batch's `split` for JPEG and Motion-JPEG input.  Runs
+    on the current GPU.  Returns the number of pairs."""
     import os
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
     _check_png_encode(png_encode)
-    frames = video.open_frames(path, png_decode)
+    frames = video.open_frames(path, png_decode, jpeg_split)
     if not torch.cuda.is_available():
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -229,13 +231,16 @@ def main(argv=None) -> int:
                     help="where the frames' PNG rows are unfiltered (the same bytes either way)")
     ap.add_argument("--png-encode", default="gpu", choices=("gpu", "host"),
                     help="where the colour images are filtered and deflated (the same pixels either way, other file bytes)")
+    ap.add_argument("--jpeg-split", default="auto", choices=("auto", "never", "always"),
+                    help="JPEG / Motion-JPEG input: decode long restart intervals (files without restart markers) a thread per segment "
+                         "(auto: from jpeg_gpu.SPLIT_MIN_BYTES bytes on; the same pixels either way)")
     ap.add_argument("--rad-max", type=float, default=None, help="one colour scale for the whole video (default: per frame)")
     a = ap.parse_args(argv)
     if not a.out and not a.video:
         ap.error("the following arguments are required: --out (or --video)")
     n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
                                       save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode,
-                                      png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality)
+                                      png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality, jpeg_split=a.jpeg_split)
     print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo) if d))
     return 0
 

@@ -335,14 +335,25 @@ def pack(parsed: Sequence[Parsed], blobs: Sequence[bytes]):
     return data, np.array(rows, np.int64).reshape(-1, DESC_WORDS), tables
 
 
-def decode_batch(blobs_or_paths: Sequence, device, threads: Optional[int] = None, names: Optional[Sequence[str]] = None) -> torch.Tensor:
+# decode_batch(split="auto"): a restart interval of at least this many bytes is decoded a thread per segment (sf_jpeg_decode_split),
+# a shorter one by one wave.  All of the project's own files (an interval per MCU row) stay below it.
+SPLIT_MIN_BYTES = 16384
+SPLIT_MODES = ("auto", "never", "always")
+
+
+def decode_batch(blobs_or_paths: Sequence, device, threads: Optional[int] = None, names: Optional[Sequence[str]] = None,
+                 split: str = "auto", segment_bytes: int = 128) -> torch.Tensor:
     """JPEG files (bytes, or paths that are read here) of ONE geometry -> uint8 [n, H, W, 3] on `device`, grey files with their sample
-    three times.  The files are read and parsed in the thread pool; the entropy-coded bytes, the descriptors and the tables go up in
+    three times.  split: "never" gives every restart interval one wave (sf_jpeg_decode); "always" decodes every interval a thread
+    per segment of segment_bytes unstuffed bytes (sf_jpeg_decode_split: what a file without restart markers needs, since it is ONE
+    interval); "auto" does that for the intervals of at least SPLIT_MIN_BYTES bytes.  The pixels are the same either way.  The files are read and parsed in the thread pool; the entropy-coded bytes, the descriptors and the tables go up in
     one copy from pinned memory; one ops.jpeg_decode call on the current stream; one read of the n status words.  ValueError for a
     file of another geometry than the first (naming it), for broken framing, and for an image the device refuses (naming it and the
     status); UnsupportedJpeg (a ValueError) for a file outside the decoder's subset.  RuntimeError without a GPU: there is no host
     decoder in this package."""
     from . import ops
+    if split not in SPLIT_MODES:
+        raise ValueError(f"jpeg_gpu.decode_batch: split = {split!r} (one of {', '.join(SPLIT_MODES)})")
     items = list(blobs_or_paths)
     if not items:
         raise ValueError("jpeg_gpu.decode_batch: no files")
@@ -382,7 +393,9 @@ def decode_batch(blobs_or_paths: Sequence, device, threads: Optional[int] = None
     with torch.cuda.device(dev):
         buf = host.to(dev, non_blocking=True)
         out, status = ops.jpeg_decode(buf[nd + nt:nd + nt + data.size], buf[:nd].view(torch.int64).view(-1, DESC_WORDS),
-                                      buf[nd:nd + nt].view(-1, TABLE_SET_BYTES), len(items), *geom)
+                                      buf[nd:nd + nt].view(-1, TABLE_SET_BYTES), len(items), *geom,
+                                      **({} if split == "never" or (split == "auto" and int(desc[:, 1].max()) < SPLIT_MIN_BYTES) else
+                                         dict(segment_bytes=segment_bytes, split_min_bytes=0 if split == "always" else SPLIT_MIN_BYTES)))
         codes = status.cpu().numpy()
     for i in np.flatnonzero(codes):
         code = int(codes[i])

@@ -1530,9 +1530,12 @@ JPEG_DESC_WORDS, JPEG_TABLE_SET_BYTES = 6, 1824
 
 @on_tensor_device
 def jpeg_decode(data: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, n_images: int, h: int, w: int, components: int, hs: int,
-                vs: int, out_channels: int = 3):
+                vs: int, out_channels: int = 3, segment_bytes: Optional[int] = None, split_min_bytes: Optional[int] = None):
     """Baseline JPEG files of one geometry -> pixels (sf_jpeg_decode, csrc/jpeg_decode.hip: Huffman decoding a wave per restart
-    interval, libjpeg's integer inverse DCT, fancy chroma upsampling, YCbCr -> RGB; the host half is jpeg_gpu.parse / pack).  data
+    interval, libjpeg's integer inverse DCT, fancy chroma upsampling, YCbCr -> RGB; the host half is jpeg_gpu.parse / pack).  With
+    segment_bytes and / or split_min_bytes it is sf_jpeg_decode_split: an interval of at least split_min_bytes (default 0: every one)
+    is decoded a thread per segment of segment_bytes (default 128; a power of two in 8 .. 4096) unstuffed bytes -- what a file without
+    restart markers needs; the pixels of an image whose status is 0 are the same either way.  data
     uint8 [B]: the entropy-coded bytes, still stuffed; desc int64 [n_intervals, 6] = (in_off, in_len, image, first_mcu, n_mcus,
     table_set) per restart interval; tables uint8 [n_sets, 1824]; all three on the same GPU.  components 1 or 3, hs x vs the luma
     sampling (1 x 1, 2 x 1, 2 x 2).  Returns (images uint8 [n_images, h, w, out_channels], status int32 [n_images]) on that GPU:
@@ -1552,7 +1555,12 @@ def jpeg_decode(data: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, n_
         raise RuntimeError(f"jpeg_decode: data, desc and tables must share a device ({data.device}, {desc.device}, {tables.device})")
     n, h, w, c, hs, vs, oc = (int(v) for v in (n_images, h, w, components, hs, vs, out_channels))
     lib = _lib.load()
-    ws_bytes = lib.sf_jpeg_decode_ws_bytes(n, h, w, c, hs, vs)
+    split = segment_bytes is not None or split_min_bytes is not None
+    seg, smin = int(128 if segment_bytes is None else segment_bytes), int(0 if split_min_bytes is None else split_min_bytes)
+    if split and (seg < 8 or seg > 4096 or seg & (seg - 1) or smin < 0):
+        raise RuntimeError(f"jpeg_decode: segment_bytes = {seg} (a power of two in 8 .. 4096), split_min_bytes = {smin} (>= 0)")
+    ws_bytes = lib.sf_jpeg_decode_split_ws_bytes(n, h, w, c, hs, vs, data.numel(), int(desc.shape[0]), seg) if split else \
+        lib.sf_jpeg_decode_ws_bytes(n, h, w, c, hs, vs)
     if ws_bytes < 0 or oc not in (1, 3):
         raise RuntimeError(f"jpeg_decode: n = {n}, h = {h}, w = {w}, components = {c}, sampling {hs} x {vs}, out_channels = {oc} is "
                            "outside what sf_jpeg_decode takes")
@@ -1560,6 +1568,11 @@ def jpeg_decode(data: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, n_
     status = torch.empty(n, dtype=torch.int32, device=data.device)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=data.device)
     # an empty tensor has no storage to point at: any non-null, never dereferenced address stands for it
+    if split:
+        _lib.check(lib.sf_jpeg_decode_split(data.data_ptr() or status.data_ptr(), data.numel(), desc.data_ptr(), int(desc.shape[0]),
+                                            tables.data_ptr(), int(tables.shape[0]), n, h, w, c, hs, vs, out.data_ptr(), h * w * oc, w * oc, oc,
+                                            status.data_ptr(), seg, smin, ws.data_ptr(), ws_bytes, _lib.stream()), "sf_jpeg_decode_split")
+        return out, status
     _lib.check(lib.sf_jpeg_decode(data.data_ptr() or status.data_ptr(), data.numel(), desc.data_ptr(), int(desc.shape[0]), tables.data_ptr(),
                                   int(tables.shape[0]), n, h, w, c, hs, vs, out.data_ptr(), h * w * oc, w * oc, oc, status.data_ptr(),
                                   ws.data_ptr(), ws_bytes, _lib.stream()), "sf_jpeg_decode")

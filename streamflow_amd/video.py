@@ -134,9 +134,14 @@ class JpegDir:
     """The baseline JPEG frames of a directory (`pattern`, default *.jpg and *.jpeg), sorted by name, as a lazy sequence.  They are
     decoded on the GPU only (jpeg_gpu.decode_batch: one sf_jpeg_decode call per batch): predict_video takes a batch's frames through
     `device_batch`, and frames[i] decodes one frame on the current GPU and returns the host array uint8 [H, W, 3] (grey replicated
-    to three channels).  All frames must have one size: the frame headers are compared when the object is made."""
+    to three channels).  All frames must have one size: the frame headers are compared when the object is made.  `split` is
+    jpeg_gpu.decode_batch's: how files without restart markers are decoded in parallel."""
 
-    def __init__(self, path: str, pattern: Optional[str] = None):
+    def __init__(self, path: str, pattern: Optional[str] = None, split: str = "auto"):
+        from .jpeg_gpu import SPLIT_MODES
+        if split not in SPLIT_MODES:
+            raise ValueError(f"JpegDir: split = {split!r} (one of {', '.join(SPLIT_MODES)})")
+        self.split = split
         patterns = JPEG_PATTERNS if pattern is None else (pattern,)
         self.paths = sorted({p for pat in patterns for p in glob.glob(os.path.join(path, pat))})
         if not self.paths:
@@ -152,7 +157,7 @@ class JpegDir:
     def device_batch(self, lo: int, hi: int, dev: torch.device) -> torch.Tensor:
         """The frames lo .. hi - 1 as uint8 [hi - lo, H, W, 3] on `dev`; raises without a GPU (there is no host decoder)."""
         from . import jpeg_gpu
-        out = jpeg_gpu.decode_batch(self.paths[lo:hi], dev)
+        out = jpeg_gpu.decode_batch(self.paths[lo:hi], dev, split=self.split)
         if tuple(out.shape[1:3]) != self.hw:
             raise ValueError(f"{self.paths[lo]}: frame size {tuple(out.shape[1:3])} differs from {self.hw}")
         return out
@@ -165,9 +170,9 @@ class JpegDir:
         return self.device_batch(i, i + 1, dev)[0].cpu().numpy()
 
 
-def open_frames(path: str, png_decode: str = "host"):
+def open_frames(path: str, png_decode: str = "host", jpeg_split: str = "auto"):
     """The frame source behind a path: a FrameDir for a directory of .png files (png_decode: its `decode`), a JpegDir for a directory
-    of .jpg / .jpeg files, an avi.MjpegReader for a file.  A directory that holds both kinds is a ValueError, one that holds neither
+    of .jpg / .jpeg files, an avi.MjpegReader for a file (jpeg_split: their `split`).  A directory that holds both kinds is a ValueError, one that holds neither
     and a path that does not exist a FileNotFoundError."""
     if os.path.isdir(path):
         png = glob.glob(os.path.join(path, "*.png"))
@@ -175,11 +180,11 @@ def open_frames(path: str, png_decode: str = "host"):
         if png and jpg:
             raise ValueError(f"{path} holds {len(png)} .png and {len(jpg)} .jpg / .jpeg frames: one kind per directory")
         if jpg:
-            return JpegDir(path)
+            return JpegDir(path, split=jpeg_split)
         return FrameDir(path, decode=png_decode)                         # raises FileNotFoundError for a directory without frames
     if os.path.isfile(path):
         from .avi import MjpegReader
-        return MjpegReader(path)
+        return MjpegReader(path, split=jpeg_split)
     raise FileNotFoundError(f"{path}: neither a directory of frames nor a video file")
 
 

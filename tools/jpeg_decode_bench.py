@@ -12,8 +12,14 @@ with a little noise so that the files are not trivially small), encoded once per
 Per set and layout, in one run on one box:
   kernel_ms          sf_jpeg_decode alone for the whole batch (a memset and four launches; inputs on the device, output and
                      workspace allocated once): device events around --launches calls after a warm-up, the median of --windows windows
-  decode_batch_ms    jpeg_gpu.decode_batch end to end from the files' bytes in memory (parse in the thread pool, one upload, the call,
-                     the read of the status words, synchronised), the median of --runs
+  split_kernel_ms    the same for sf_jpeg_decode_split with every interval split (split_min_bytes = 0), per segment_bytes in 64, 128,
+                     256: {segment_bytes: ms}; split_over_wave = kernel_ms / the best of them
+  decode_batch_ms    jpeg_gpu.decode_batch(split="never") -- a wave per interval, the route before the split route existed -- end to
+                     end from the files' bytes in memory (parse in the thread pool, one upload, the call, the read of the status words,
+                     synchronised), the median of --runs; decode_batch_split_ms the same with split="always", the two taken in turn
+                     in the same loop; decode_batch_spread the largest (max - min) / median of the two run lists
+  sync               for the first file at each segment size, from the sanitized host program that runs the kernels' functions
+                     (csrc/host/jpeg_sync_host_main.cpp): segments, rounds and re-decodes beyond the speculative pass
   pil_loop_ms        PIL's decode of every file, one thread, np.stack and one upload of the batch; the median of --runs; "skipped"
                      where PIL is absent
 and for the `rows` layout of the first set the whole from a file to flows:
@@ -21,7 +27,7 @@ and for the `rows` layout of the first set the whole from a file to flows:
                      T = 4, 8 clips per call, --iters) on an avi.MjpegReader over the written AVI file, and on the decoded frames
                      already on the device; the median of --runs
 Before anything is timed every layout's pixels are compared: decode_batch against PIL's bit for bit where PIL is there, and the
-first frame of `rows` against tests/jpeg_decode_cases.decode_ref.  The numbers are reported, not gated.  One JSON line per set and
+first frame of `rows` against tests/jpeg_decode_cases.decode_ref; split="always" against split="never" bit for bit.  The numbers are reported, not gated.  One JSON line per set and
 layout, written to --out.  Needs no dataset; a GPU is required (no fallback)."""
 import argparse
 import io
@@ -37,9 +43,11 @@ import torch
 
 from streamflow_amd import _lib, avi, jpeg_gpu, ops, png_gpu, video
 from tests import jpeg_decode_cases as dc
+from tests import jpeg_sync_cases as sc
 from tests import png_encode_cases as ec
 
 SETS = [("frames_436x1024", 24, 436, 1024), ("frames_1088x1920", 3, 1088, 1920)]
+SEGMENT_BYTES = (64, 128, 256)
 
 
 def median_ms(fn, runs):
@@ -79,6 +87,7 @@ def main(argv=None) -> int:
     pil_q = [[int(v) for v in t] for t in q]
     lines = []
     with tempfile.TemporaryDirectory() as tmp:
+        host = sc.host_program(tmp)
         for name, n, h, w in SETS:
             flows = torch.from_numpy(np.stack([ec.smooth_field(h, w, 100 + i) for i in range(n)])).to(dev)
             clean = ops.flow_to_image(flows).cpu().numpy().astype(np.int16)
@@ -98,7 +107,8 @@ def main(argv=None) -> int:
                        "file_bytes": sum(len(f) for f in files), "raw_bytes": n * h * w * 3}
                 parsed = [jpeg_gpu.parse(f) for f in files]
                 rec["intervals_per_image"] = len(parsed[0].intervals)
-                got = jpeg_gpu.decode_batch(files, dev)
+                got = jpeg_gpu.decode_batch(files, dev, split="never")
+                assert torch.equal(jpeg_gpu.decode_batch(files, dev, split="always"), got), (name, tag)
 
                 def pil_loop():
                     return torch.from_numpy(np.stack([np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in files])).to(dev)
@@ -106,7 +116,13 @@ def main(argv=None) -> int:
                 if Image is not None:
                     assert torch.equal(got, pil_loop()), (name, tag)
                     rec["equals_pil"] = True
-                rec["decode_batch_ms"], rec["decode_batch_ms_runs"] = median_ms(lambda: jpeg_gpu.decode_batch(files, dev), a.runs)
+                never, always = [], []
+                for _ in range(a.runs):                                 # in turn, so that drift hits both alike
+                    never += median_ms(lambda: jpeg_gpu.decode_batch(files, dev, split="never"), 1)[1]
+                    always += median_ms(lambda: jpeg_gpu.decode_batch(files, dev, split="always"), 1)[1]
+                rec["decode_batch_ms"], rec["decode_batch_ms_runs"] = round(float(np.median(never)), 2), never
+                rec["decode_batch_split_ms"], rec["decode_batch_split_ms_runs"] = round(float(np.median(always)), 2), always
+                rec["decode_batch_spread"] = round(max((max(r) - min(r)) / np.median(r) for r in (never, always)), 3)
                 if Image is not None:
                     rec["pil_loop_ms"], rec["pil_loop_ms_runs"] = median_ms(pil_loop, a.runs)
                     rec["pil_loop_over_decode_batch"] = round(rec["pil_loop_ms"] / rec["decode_batch_ms"], 2)
@@ -114,32 +130,59 @@ def main(argv=None) -> int:
                     rec["pil_loop_ms"] = "skipped"
                 data, desc, tables = (torch.from_numpy(x.copy()).to(dev) for x in jpeg_gpu.pack(parsed, files))
                 geom = parsed[0][:5]
-                ws_bytes = lib.sf_jpeg_decode_ws_bytes(n, *geom)
                 out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
                 status = torch.empty(n, dtype=torch.int32, device=dev)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+                head = (data.data_ptr(), data.numel(), desc.data_ptr(), desc.shape[0], tables.data_ptr(), tables.shape[0], n, *geom, out.data_ptr(),
+                        h * w * 3, w * 3, 3, status.data_ptr())
 
-                def call():
-                    _lib.check(lib.sf_jpeg_decode(data.data_ptr(), data.numel(), desc.data_ptr(), desc.shape[0], tables.data_ptr(), tables.shape[0],
-                                                  n, *geom, out.data_ptr(), h * w * 3, w * 3, 3, status.data_ptr(), ws.data_ptr(), ws_bytes,
-                                                  _lib.stream()), "sf_jpeg_decode")
+                def timed(segment_bytes):
+                    """ms per call of sf_jpeg_decode (segment_bytes None) or sf_jpeg_decode_split with every interval split."""
+                    ws_bytes = lib.sf_jpeg_decode_ws_bytes(n, *geom) if segment_bytes is None else \
+                        lib.sf_jpeg_decode_split_ws_bytes(n, *geom, data.numel(), desc.shape[0], segment_bytes)
+                    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
 
-                for _ in range(3):
-                    call()
-                torch.cuda.synchronize()
-                assert not status.any() and torch.equal(out, got), (name, tag)
-                windows = []
-                for _ in range(a.windows):
-                    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    s.record()
-                    for _ in range(a.launches):
+                    def call():
+                        if segment_bytes is None:
+                            _lib.check(lib.sf_jpeg_decode(*head, ws.data_ptr(), ws_bytes, _lib.stream()), "sf_jpeg_decode")
+                        else:
+                            _lib.check(lib.sf_jpeg_decode_split(*head, segment_bytes, 0, ws.data_ptr(), ws_bytes, _lib.stream()), "sf_jpeg_decode_split")
+
+                    out.zero_()
+                    for _ in range(3):
                         call()
-                    e.record()
-                    e.synchronize()
-                    windows.append(s.elapsed_time(e) / a.launches)
-                kernel_ms = float(np.median(windows))
-                rec.update({"kernel_ms": round(kernel_ms, 4), "kernel_ms_windows": [round(x, 4) for x in windows],
+                    torch.cuda.synchronize()
+                    assert not status.any() and torch.equal(out, got), (name, tag, segment_bytes)
+                    windows = []
+                    for _ in range(a.windows):
+                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        s.record()
+                        for _ in range(a.launches):
+                            call()
+                        e.record()
+                        e.synchronize()
+                        windows.append(s.elapsed_time(e) / a.launches)
+                    return float(np.median(windows)), [round(x, 4) for x in windows], ws_bytes
+
+                kernel_ms, windows, ws_bytes = timed(None)
+                rec.update({"kernel_ms": round(kernel_ms, 4), "kernel_ms_windows": windows,
                             "kernel_MPix_per_s": round(n * h * w / kernel_ms / 1e3, 1), "workspace_bytes": ws_bytes})
+                split = {S: timed(S) for S in SEGMENT_BYTES}
+                rec["split_kernel_ms"] = {str(S): round(v[0], 4) for S, v in split.items()}
+                rec["split_kernel_ms_windows"] = {str(S): v[1] for S, v in split.items()}
+                rec["split_workspace_bytes"] = {str(S): v[2] for S, v in split.items()}
+                rec["split_over_wave"] = round(kernel_ms / min(v[0] for v in split.values()), 2)
+                rec["interval_bytes_max"] = int(desc[:, 1].max())
+                first = [parsed[0]], [files[0]]
+                rec["sync"] = {}
+                for S in SEGMENT_BYTES:
+                    c = object.__new__(sc.Call)
+                    c.h, c.w, c.nc, c.hs, c.vs = geom
+                    c.n, c.names = 1, [name]
+                    c.data, c.desc, c.tables = jpeg_gpu.pack(*first)
+                    c.segment_bytes, c.split_min_bytes = S, 0
+                    r = sc.run_host(host, [c], tmp, "sync")[0]
+                    rec["sync"][str(S)] = {"segments": int(r["segments"].sum()), "rounds_max": int(r["rounds"].max()),
+                                           "redecodes": int(r["redecodes"].sum())}
                 if tag == "rows" and name == SETS[0][0]:
                     from streamflow_amd import synthetic as syn
                     from streamflow_amd.model import SKFlow_MF8, default_args
