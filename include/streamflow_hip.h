@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 135
+#define SF_VERSION 136
 
 enum {
     SF_OK = 0,
@@ -850,6 +850,66 @@ int sf_frames_to_clips(const uint8_t* frames, int64_t frame_stride, int64_t row_
 int sf_clips_to_flows(const SfPairPtrs* pairs, int64_t clip_stride, int64_t ch_stride, int64_t row_stride, int n, int T,
                       int first_clip, int n_clips, int pair0, int n_pairs, int H, int W, int pad_top, int pad_left, float* out,
                       void* stream);
+
+/* ---- forward-backward consistency: occlusion classes and backward warping, a batch of fields per call -------------------------
+ * The consistency check of Sundaram et al. 2010 with the constants' roles as in UnFlow (Meister et al. 2018).  Both entry points
+ * share one coordinate rule.  For pixel (y, x) of field i with flow (u, v), fp32, every operation rounded on its own:
+ *     px = (float)x + u,  py = (float)y + v,
+ *     inside = px >= 0 && px <= (float)(w - 1) && py >= 0 && py <= (float)(h - 1)        (false for NaN; made BEFORE any conversion
+ *              to an integer, so NaN, +-Inf and huge flows never form an address),
+ *     x0 = floorf(px), fx = px - x0, x1 = min(x0 + 1, w - 1), likewise y0, fy, y1,
+ *     sample(A) = (1 - fy) * ((1 - fx) * A[y0][x0] + fx * A[y0][x1]) + fy * ((1 - fx) * A[y1][x0] + fx * A[y1][x1])   in this order.
+ *
+ * sf_flow_consistency: n forward and n backward fields of one size h x w, fp32 planes: u of field i at
+ *   fwd + i fwd_field_stride + y fwd_row_stride + x, v at the same + fwd_ch_stride (strides in floats; bwd likewise: slices of
+ *   predict_video's outputs and views into padded buffers need no copy).  Inside:
+ *     bu = sample(bwd u), bv = sample(bwd v),  dx = u + bu, dy = v + bv,  lhs = dx dx + dy dy,
+ *     rhs = alpha * ((u u + v v) + (bu bu + bv bv)) + beta,
+ *   class VISIBLE if inside && lhs <= rhs; OCCLUDED if inside && !(lhs <= rhs) (a NaN among the taps included); OUTSIDE otherwise.
+ *   cls:   uint8 [n][h][w] dense; the byte of a pixel is code_visible / code_occluded / code_outside (255 / 0 / 128 gives a mask
+ *          image, 0 / 1 / 2 codes, without a second pass).
+ *   stats: fp64 [n][SF_FBC_LEN] on the device; row i is ADDED to (counts are exact in fp64 below 2^53):
+ *            PIXELS    pixels                         VISIBLE / OCCLUDED / OUTSIDE   pixels of each class
+ *            SUM_FB    sum of sqrtf(lhs) over visible pixels
+ *            SUM_MAG   sum of sqrtf(u u + v v) over the pixels where that magnitude is finite in fp32 (NaN, Inf and flows whose
+ *                      square overflows stay out)     FINITE   their number
+ *   ws:    scratch of sf_flow_consistency_ws_bytes(n, h, w) bytes (per-block partials); it is not read by later calls.
+ *   Consecutive lanes take consecutive pixels (coalesced element loads and stores for any strides and alignment, measured faster
+ *   than four pixels per lane with 16-byte accesses); the taps of the backward field are element loads (a gather).
+ *
+ * sf_warp_frames: n source frames (in a video: the frames j + 1), uint8 with 3 channels, byte (i, y, x, ch) at
+ *   src + i src_frame_stride + y src_row_stride + x src_px_stride + ch src_ch_stride (bytes, >= 0, as sf_frames_to_clips: HWC, CHW
+ *   and views), warped back by field i of `flows` (planes addressed as fwd above):
+ *     val = sample((float)src channel),   out[i][y][x][ch] = (uint8)floorf(val + 0.5f) inside, 0 outside;   out uint8 [n][h][w][3] dense.
+ *   cls (sf_flow_consistency's map for the same flows) and ref (the frames j, strides as src) are optional and come together; with
+ *   them row i of stats fp64 [n][SF_WARP_LEN] is ADDED to: SUM_ABS = sum over inside pixels whose class byte is code_visible, and
+ *   over the three channels, of fabsf(val - (float)ref byte); TERMS = the number of terms.  ws: sf_warp_frames_ws_bytes(n, h, w)
+ *   bytes; stats and ws may be NULL without cls / ref.  float4 loads of the flow planes where pointer and strides allow, three 4-byte
+ *   stores per four pixels where w % 4 == 0 and out is 4-byte aligned; element accesses otherwise.
+ *
+ * Both: one main launch (grid: blocks per field x n) and, with stats, one finish launch (a block per field sums the per-block
+ * partials in a fixed order); no atomics; the grid depends on (n, h, w) alone, so repeated calls give bitwise equal rows.  Enqueued
+ * on `stream`, no host synchronisation.
+ * SF_ERR_BAD_ARG before any launch for: null pointers (cls without ref or the reverse; stats or ws missing where they are needed);
+ * h, w <= 0, h * w >= 2^30, n outside 1 .. 65535; a flow row stride < w, a zero channel stride, negative field / byte strides; NaN
+ * alpha or beta; flow pointers not 4-byte, stats / ws not 8-byte aligned; ws_bytes too small.  The *_ws_bytes functions return
+ * SF_ERR_BAD_ARG for n, h, w outside the limits. */
+enum {
+    SF_FBC_PIXELS = 0, SF_FBC_VISIBLE = 1, SF_FBC_OCCLUDED = 2, SF_FBC_OUTSIDE = 3, SF_FBC_SUM_FB = 4, SF_FBC_SUM_MAG = 5,
+    SF_FBC_FINITE = 6, SF_FBC_LEN = 7
+};
+enum { SF_WARP_SUM_ABS = 0, SF_WARP_TERMS = 1, SF_WARP_LEN = 2 };
+int64_t sf_flow_consistency_ws_bytes(int n, int h, int w);
+int sf_flow_consistency(const float* fwd, int64_t fwd_field_stride, int64_t fwd_ch_stride, int64_t fwd_row_stride, const float* bwd,
+                        int64_t bwd_field_stride, int64_t bwd_ch_stride, int64_t bwd_row_stride, int n, int h, int w, float alpha,
+                        float beta, uint8_t code_visible, uint8_t code_occluded, uint8_t code_outside, uint8_t* cls, double* stats,
+                        void* ws, int64_t ws_bytes, void* stream);
+int64_t sf_warp_frames_ws_bytes(int n, int h, int w);
+int sf_warp_frames(const uint8_t* src, int64_t src_frame_stride, int64_t src_row_stride, int64_t src_px_stride, int64_t src_ch_stride,
+                   const float* flows, int64_t flow_field_stride, int64_t flow_ch_stride, int64_t flow_row_stride, int n, int h, int w,
+                   uint8_t* out, const uint8_t* cls, uint8_t code_visible, const uint8_t* ref, int64_t ref_frame_stride,
+                   int64_t ref_row_stride, int64_t ref_px_stride, int64_t ref_ch_stride, double* stats, void* ws, int64_t ws_bytes,
+                   void* stream);
 
 /* ---- PNG frames: row unfiltering of inflated IDAT streams (PNG specification, section 9; flow_io.read_png on the host) ----------
  * The host inflates (zlib); the device undoes the row filters of a whole batch of equally shaped images in one launch, so the

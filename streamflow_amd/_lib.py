@@ -192,6 +192,12 @@ SIGNATURES = {
     "sf_flow_score": (_i, [_vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "sf_flow_score_batch_ws_bytes": (_i64, [_i, _i, _i]),
     "sf_flow_score_batch": (_i, [C.POINTER(SfScoreFields), _i, _i64, _i64, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "sf_flow_consistency_ws_bytes": (_i64, [_i, _i, _i]),
+    "sf_flow_consistency": (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _f, _f, C.c_uint8, C.c_uint8, C.c_uint8, _vp, _vp,
+                                 _vp, _i64, _vp]),
+    "sf_warp_frames_ws_bytes": (_i64, [_i, _i, _i]),
+    "sf_warp_frames": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, C.c_uint8, _vp, _i64, _i64, _i64,
+                            _i64, _vp, _vp, _i64, _vp]),
     "sf_frames_to_clips": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_clips_to_flows": (_i, [C.POINTER(SfPairPtrs), _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sf_png_unfilter": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp]),
@@ -236,7 +242,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 135:
+    if lib.sf_version() < 136:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -160,7 +160,8 @@ def vis_flow_video(flows_result: Sequence[torch.Tensor], save_path: str = "flow_
 def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, clips_per_step: int = 8, mode: str = "sintel",
                                   save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host",
                                   png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90,
-                                  jpeg_split: str = "auto") -> int:
+                                  jpeg_split: str = "auto", bidirectional: bool = False, occlusion_dir: str = None,
+                                  warp_dir: str = None, report: bool = False) -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
     baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
@@ -170,7 +171,13 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     (png_gpu.encode_batch: no uncompressed image crosses to the host; the same pixels, other file bytes).  With `video_path` every
     batch's images are also encoded as JPEG frames on the GPU (IJG quality `jpeg_quality`) and appended to one Motion-JPEG AVI file
     of `fps` frames per second (avi.MjpegWriter).  jpeg_split: jpeg_gpu.decode_batch's `split` for JPEG and Motion-JPEG input.  Runs
-    on the current GPU.  Returns the number of pairs."""
+    on the current GPU.  Returns the number of pairs.
+
+    bidirectional: the backward flows too (video.predict_video(..., bidirectional=True)); with `flo_dir` they are written as
+    ``frame_%04d_bwd.flo``.  occlusion_dir: the forward-backward consistency classes of every pair as 8-bit grey
+    ``frame_%04d.png`` (255 visible, 0 occluded, 128 outside the frame; consistency.MASK_CODES), written where `png_encode` says.
+    warp_dir: frame j + 1 warped onto frame j as RGB ``frame_%04d.png``.  report: consistency.video_report's lines are printed at
+    the end.  The last three imply bidirectional; without any of them nothing changes."""
     import os
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
@@ -180,7 +187,8 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
     model = StreamFlowT4(ckpt).to(device).eval()
-    for d in (save_dir, flo_dir):
+    bidirectional = bool(bidirectional or occlusion_dir or warp_dir or report)
+    for d in (save_dir, flo_dir, occlusion_dir, warp_dir):
         if d:
             os.makedirs(d, exist_ok=True)
     written = [0]
@@ -203,15 +211,57 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
             _add_video_frames(writer[0], list(flows), rad_max, jpeg_quality)
         written[0] += int(flows.shape[0])
 
+    def write_images(images: torch.Tensor, directory: str, first_pair: int) -> None:
+        """Device images uint8 [k, H, W, C] as directory/frame_%04d.png (grey for C = 1)."""
+        from . import png_gpu
+        paths = [os.path.join(directory, "frame_%04d.png" % (first_pair + k)) for k in range(images.shape[0])]
+        if png_encode == "gpu":
+            png_gpu.encode_batch(images.contiguous(), paths)
+        else:
+            host = images.cpu().numpy()
+            for k, p in enumerate(paths):
+                flow_io.write_png(p, host[k, :, :, 0] if host.shape[3] == 1 else host[k])
+
+    def then(first_pair, fwd, bwd, held, classes, warped) -> None:
+        if occlusion_dir:
+            write_images(classes[0][..., None], occlusion_dir, first_pair)
+        if warp_dir:
+            write_images(warped[0], warp_dir, first_pair)
+
+    from . import consistency
+    reporter = consistency.ReportSink(then=then) if report else None
+
+    def sink_both(first_pair: int, fwd: torch.Tensor, bwd: torch.Tensor, held: torch.Tensor) -> None:
+        sink(first_pair, fwd)
+        if flo_dir:
+            host = bwd.cpu().numpy()
+            for k in range(host.shape[0]):
+                flow_io.write_flo(os.path.join(flo_dir, "frame_%04d_bwd.flo" % (first_pair + k)), host[k].transpose(1, 2, 0))
+        if reporter is not None:
+            reporter(first_pair, fwd, bwd, held)
+        elif occlusion_dir or warp_dir:
+            from . import ops
+            cls = ops.flow_consistency(fwd, bwd, consistency.ALPHA, consistency.BETA, consistency.MASK_CODES)[0] if occlusion_dir else None
+            warped = consistency.warp_back(held, fwd)[0] if warp_dir else None
+            then(first_pair, fwd, bwd, held, (cls, None), (warped, None))
+
     try:
-        video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink)
+        if bidirectional:
+            video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device,
+                                sink=sink_both, bidirectional=True)
+        else:
+            video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink)
     finally:
         if writer:
             writer[0].close()
+    if reporter is not None:
+        rep = reporter.report()
+        for name in consistency.DIRECTIONS:
+            print(consistency.report_line(name, rep[name]))
     return written[0]
 
 
-def main(argv=None) -> int:
+def arg_parser():
     import argparse
     ap = argparse.ArgumentParser(prog="python -m streamflow_amd.demo",
                                  description="Flow fields of a directory of PNG or JPEG frames or a Motion-JPEG AVI file, as colour-wheel PNGs, a Motion-JPEG AVI "
@@ -235,13 +285,28 @@ def main(argv=None) -> int:
                     help="JPEG / Motion-JPEG input: decode long restart intervals (files without restart markers) a thread per segment "
                          "(auto: from jpeg_gpu.SPLIT_MIN_BYTES bytes on; the same pixels either way)")
     ap.add_argument("--rad-max", type=float, default=None, help="one colour scale for the whole video (default: per frame)")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="also the backward flows (every clip batch is run time-reversed too); with --flo: frame_%%04d_bwd.flo")
+    ap.add_argument("--occlusion", default=None, metavar="DIR",
+                    help="directory for the forward-backward consistency masks frame_%%04d.png, 8-bit grey: 255 visible, 0 occluded, "
+                         "128 outside the frame (implies --bidirectional)")
+    ap.add_argument("--warp", default=None, metavar="DIR",
+                    help="directory for frame j + 1 warped onto frame j, RGB frame_%%04d.png (implies --bidirectional)")
+    ap.add_argument("--report", action="store_true",
+                    help="print the consistency report of the video, one line per direction (implies --bidirectional)")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = arg_parser()
     a = ap.parse_args(argv)
     if not a.out and not a.video:
         ap.error("the following arguments are required: --out (or --video)")
     n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
                                       save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode,
-                                      png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality, jpeg_split=a.jpeg_split)
-    print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo) if d))
+                                      png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality, jpeg_split=a.jpeg_split,
+                                      bidirectional=a.bidirectional, occlusion_dir=a.occlusion, warp_dir=a.warp, report=a.report)
+    print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp) if d))
     return 0
 
 

@@ -1424,6 +1424,130 @@ def clips_to_flows(pairs: Sequence[torch.Tensor], n: int, T: int, first_clip: in
     return out
 
 
+FBC_LEN, WARP_LEN = 7, 2     # SF_FBC_LEN, SF_WARP_LEN: doubles per stats row of flow_consistency / warp_frames
+FBC_PIXELS, FBC_VISIBLE, FBC_OCCLUDED, FBC_OUTSIDE, FBC_SUM_FB, FBC_SUM_MAG, FBC_FINITE = range(7)
+WARP_SUM_ABS, WARP_TERMS = range(2)
+
+
+def _flow_fields(t, name: str, what: str):
+    """Checks of a batch of flow fields fp32 [n, 2, h, w] with contiguous rows -> (n, h, w)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what}: {name} must be a tensor on the GPU (got {getattr(t, 'device', type(t).__name__)}); "
+                           "there is no CPU fallback")
+    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 2 or t.numel() == 0 or t.stride(3) != 1:
+        raise RuntimeError(f"{what}: {name} must be fp32 [n, 2, h, w] with contiguous rows (got {t.dtype} {tuple(t.shape)}, "
+                           f"strides {t.stride()})")
+    if t.stride(2) < t.shape[3] or t.stride(0) < 0 or t.stride(1) == 0:
+        raise RuntimeError(f"{what}: {name} has strides {t.stride()} (rows must not overlap)")
+    return int(t.shape[0]), int(t.shape[2]), int(t.shape[3])
+
+
+def _stats_rows(stats, n: int, length: int, dev, what: str) -> torch.Tensor:
+    if stats is None:
+        return torch.zeros(n, length, dtype=torch.float64, device=dev)
+    if (not isinstance(stats, torch.Tensor) or stats.device != dev or stats.dtype != torch.float64 or tuple(stats.shape) != (n, length)
+            or not stats.is_contiguous()):
+        raise RuntimeError(f"{what}: stats must be contiguous float64 [{n}, {length}] on {dev} "
+                           f"(got {getattr(stats, 'dtype', None)} {tuple(getattr(stats, 'shape', ()))})")
+    return stats
+
+
+def _frame_strides(t, name: str, channels_last, hw, n: int, dev, what: str):
+    """Checks of a batch of uint8 frames [n, H, W, 3] / [n, 3, H, W] -> byte strides (frame, row, pixel, channel)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what}: {name} must be a tensor on the GPU (got {getattr(t, 'device', type(t).__name__)}); "
+                           "there is no CPU fallback")
+    if t.dtype != torch.uint8 or t.dim() != 4:
+        raise RuntimeError(f"{what}: {name} must be uint8 [n, H, W, 3] or [n, 3, H, W] (got {t.dtype} {tuple(t.shape)})")
+    if channels_last is None:
+        channels_last = t.shape[3] == 3
+    if t.shape[3 if channels_last else 1] != 3:
+        raise RuntimeError(f"{what}: no channel dimension of 3 in {name} {tuple(t.shape)} (channels_last={channels_last})")
+    fs = t.stride(0)
+    if channels_last:
+        shape, (rs, ps, cs) = tuple(t.shape[1:3]), t.stride()[1:]
+    else:
+        shape, (cs, rs, ps) = tuple(t.shape[2:]), t.stride()[1:]
+    if int(t.shape[0]) != n or tuple(int(v) for v in shape) != tuple(hw) or t.device != dev:
+        raise RuntimeError(f"{what}: {name} holds {int(t.shape[0])} frames of {tuple(shape)} on {t.device}, the flows are {n} fields of "
+                           f"{tuple(hw)} on {dev}")
+    if min(fs, rs, ps, cs) < 0:
+        raise RuntimeError(f"{what}: {name} has a negative stride {t.stride()}")
+    return fs, rs, ps, cs
+
+
+@on_tensor_device
+def flow_consistency(fwd: torch.Tensor, bwd: torch.Tensor, alpha: float = 0.01, beta: float = 0.5, codes: Sequence[int] = (0, 1, 2),
+                     stats: Optional[torch.Tensor] = None):
+    """Forward-backward consistency classes of n flow fields (sf_flow_consistency, two launches for the whole batch): fwd, bwd fp32
+    [n, 2, h, w] on one GPU, any views with contiguous rows (slices of predict_video's outputs need no copy); bwd[i] is the flow
+    that leads back from the frame fwd[i] leads to.  A pixel is visible when |fwd + bwd(x + fwd)|^2 <= alpha (|fwd|^2 + |bwd|^2) +
+    beta (alpha, beta: the constants of Sundaram et al. 2010 / UnFlow), occluded when not, outside when x + fwd leaves the frame (NaN
+    and infinite flows included).  codes = the bytes written for (visible, occluded, outside); (255, 0, 128) gives a mask image.
+    Returns (cls uint8 [n, h, w], stats float64 [n, FBC_LEN]); a given `stats` is ADDED to (rows: FBC_PIXELS, FBC_VISIBLE,
+    FBC_OCCLUDED, FBC_OUTSIDE, FBC_SUM_FB, FBC_SUM_MAG, FBC_FINITE; include/streamflow_hip.h).  Enqueued on the current stream,
+    no synchronisation."""
+    what = "flow_consistency"
+    n, h, w = _flow_fields(fwd, "fwd", what)
+    if _flow_fields(bwd, "bwd", what) != (n, h, w) or bwd.device != fwd.device:
+        raise RuntimeError(f"{what}: fwd is {tuple(fwd.shape)} on {fwd.device}, bwd {tuple(bwd.shape)} on {bwd.device}")
+    codes = tuple(int(c) for c in codes)
+    if len(codes) != 3 or any(not 0 <= c <= 255 for c in codes):
+        raise RuntimeError(f"{what}: codes must be three byte values (visible, occluded, outside), got {codes}")
+    if alpha != alpha or beta != beta:
+        raise RuntimeError(f"{what}: alpha / beta is NaN")
+    dev = fwd.device
+    stats = _stats_rows(stats, n, FBC_LEN, dev, what)
+    lib = _lib.load()
+    cls = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(lib.sf_flow_consistency_ws_bytes(n, h, w)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.sf_flow_consistency(fwd.data_ptr(), fwd.stride(0), fwd.stride(1), fwd.stride(2), bwd.data_ptr(), bwd.stride(0),
+                                       bwd.stride(1), bwd.stride(2), n, h, w, float(alpha), float(beta), codes[0], codes[1], codes[2],
+                                       cls.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream()),
+               "sf_flow_consistency")
+    return cls, stats
+
+
+@on_tensor_device
+def warp_frames(src: torch.Tensor, flows: torch.Tensor, cls: Optional[torch.Tensor] = None, ref: Optional[torch.Tensor] = None,
+                channels_last: Optional[bool] = None, stats: Optional[torch.Tensor] = None, visible: int = 0):
+    """Frames warped back along flow fields (sf_warp_frames): src uint8 [n, H, W, 3] or [n, 3, H, W] on the GPU, any strides
+    (`channels_last` decides when both readings fit, default: HWC if the last dimension is 3); flows fp32 [n, 2, H, W] with contiguous
+    rows, flows[i] leading from the frame the result is aligned with to src[i] (in a video: src = frames 1 .. n, flows = the forward
+    flows).  Returns (warped uint8 [n, H, W, 3]: bilinear taps rounded to nearest, 0 where the target leaves the frame; stats).
+    With `cls` (flow_consistency's map for the same flows, uint8 [n, H, W] contiguous, `visible` = its byte for visible pixels) and
+    `ref` (the frames the result is aligned with, laid out like src) the photometric error is ADDED into stats float64 [n, WARP_LEN]:
+    WARP_SUM_ABS = sum of |warped value - ref byte| over visible pixels and channels, WARP_TERMS = the number of terms; without
+    them stats is None.  Enqueued on the current stream, no synchronisation."""
+    what = "warp_frames"
+    n, h, w = _flow_fields(flows, "flows", what)
+    dev = flows.device
+    s = _frame_strides(src, "src", channels_last, (h, w), n, dev, what)
+    if (cls is None) != (ref is None):
+        raise RuntimeError(f"{what}: cls and ref come together (got cls={'given' if cls is not None else None}, "
+                           f"ref={'given' if ref is not None else None})")
+    if cls is None and stats is not None:
+        raise RuntimeError(f"{what}: stats without cls and ref")
+    lib = _lib.load()
+    r, ws, cls_ptr, ref_ptr = (0, 0, 0, 0), None, None, None
+    if cls is not None:
+        if not cls.is_cuda or cls.device != dev or cls.dtype != torch.uint8 or tuple(cls.shape) != (n, h, w) or not cls.is_contiguous():
+            raise RuntimeError(f"{what}: cls must be contiguous uint8 [{n}, {h}, {w}] on {dev} (got {cls.dtype} {tuple(cls.shape)} on "
+                               f"{cls.device}); there is no CPU fallback")
+        if not 0 <= int(visible) <= 255:
+            raise RuntimeError(f"{what}: visible must be a byte value, got {visible}")
+        r = _frame_strides(ref, "ref", channels_last, (h, w), n, dev, what)
+        stats = _stats_rows(stats, n, WARP_LEN, dev, what)
+        ws = torch.empty(int(lib.sf_warp_frames_ws_bytes(n, h, w)), dtype=torch.uint8, device=dev)
+        cls_ptr, ref_ptr = cls.data_ptr(), ref.data_ptr()
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    _lib.check(lib.sf_warp_frames(src.data_ptr(), s[0], s[1], s[2], s[3], flows.data_ptr(), flows.stride(0), flows.stride(1),
+                                  flows.stride(2), n, h, w, out.data_ptr(), cls_ptr, int(visible), ref_ptr, r[0], r[1], r[2], r[3],
+                                  None if stats is None else stats.data_ptr(), None if ws is None else ws.data_ptr(),
+                                  0 if ws is None else ws.numel(), _lib.stream()), "sf_warp_frames")
+    return out, stats
+
+
 PNG_BPP = (1, 2, 3, 4, 6, 8)          # PNG filter distances sf_png_unfilter is built for: 8 / 16-bit grey, grey + alpha, RGB, RGBA
 
 

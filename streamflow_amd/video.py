@@ -257,7 +257,7 @@ class _Source:
 
 @torch.no_grad()
 def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = None, clips_per_step: int = 8, mode: str = "sintel",
-                  device=None, sink: Optional[Callable[[int, torch.Tensor], None]] = None) -> Optional[torch.Tensor]:
+                  device=None, sink: Optional[Callable[..., None]] = None, bidirectional: bool = False):
     """Flow fields of every consecutive frame pair of a video, `clips_per_step` clips per model call.
 
     frames: a uint8 tensor / array [N, H, W, 3] or [N, 3, H, W] (HWC when both readings fit) on the host or the GPU, or a sequence
@@ -267,7 +267,15 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
     frames' GPU, else the model's, else the current one.
 
     Returns a device tensor [N - 1, 2, H, W]; with `sink`, calls `sink(first_pair, flows[k, 2, H, W])` per batch in video order,
-    keeps nothing and returns None (long videos, writing to disk).  Nothing here synchronises with the host."""
+    keeps nothing and returns None (long videos, writing to disk).  Nothing here synchronises with the host.
+
+    bidirectional=True: every batch's clip tensor is also run time-reversed (`imgs.flip(1)`, a second model call of the same batch
+    size: an engine's plan and graph are reused, `clips_per_step` keeps its memory meaning) and the result is `(fwd, bwd)`, both
+    [N - 1, 2, H, W].  bwd[j] is the flow from frame j + 1 to frame j, computed from the REVERSED clip that holds pair j in the
+    forward schedule (slot T - 2 - k of the reversed clip for slot k of the forward one).  It is not predict_video on the reversed
+    video, whose clip boundaries differ when (N - 1) % (T - 1) != 0.  With `sink` the call is `sink(first_pair, fwd, bwd, frames)`:
+    frames is the uint8 device tensor [k + 1, H, W, 3] of the frames first_pair .. first_pair + k (a view of the batch's frame
+    buffer).  streamflow_amd.consistency turns the two fields into occlusion masks, warped frames and a report."""
     from . import ops
     src = _Source(frames)
     if T < 2 or T - 1 > MAX_PAIRS:
@@ -289,6 +297,7 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
     pad = InputPadder((H, W), mode=mode)._pad
     call = batched_call(model, iters)
     out = None if sink is not None else torch.empty(src.n - 1, 2, H, W, dtype=torch.float32, device=dev)
+    out_b = torch.empty_like(out) if bidirectional and out is not None else None
     with torch.cuda.device(dev):
         for first, k, f_lo, f_hi, p_lo, p_hi in batches:
             buf, channels_last, frame0 = src.device_frames(f_lo, f_hi, dev)
@@ -298,6 +307,16 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
                 raise RuntimeError(f"predict_video: the model returned {len(flows)} flows for clips of T = {T}")
             got = ops.clips_to_flows(flows, src.n, T, first, p_lo, p_hi - p_lo, (H, W), pad,
                                      out=None if out is None else out[p_lo:p_hi])
+            if not bidirectional:
+                if sink is not None:
+                    sink(p_lo, got)
+                continue
+            back = list(call(imgs.flip(1)))
+            if len(back) != T - 1:
+                raise RuntimeError(f"predict_video: the model returned {len(back)} flows for reversed clips of T = {T}")
+            got_b = ops.clips_to_flows(back[::-1], src.n, T, first, p_lo, p_hi - p_lo, (H, W), pad,
+                                       out=None if out_b is None else out_b[p_lo:p_hi])
             if sink is not None:
-                sink(p_lo, got)
-    return out
+                held = buf[p_lo - frame0:p_hi + 1 - frame0]
+                sink(p_lo, got, got_b, held if channels_last else held.permute(0, 2, 3, 1))
+    return (out, out_b) if bidirectional and sink is None else out
