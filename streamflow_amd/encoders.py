@@ -150,9 +150,11 @@ class Twins_CSC(nn.Module):
         return self._pack
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, precision=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, precision=None, taps=None) -> torch.Tensor:
         """precision: 'fp32' | 'f16x3' | 'f16x2' | 'f16' (or the integer constant): the arithmetic class of this call; None = the
-        package default (ops.PRECISION).  Passed explicitly to every launch: the module keeps no launch state."""
+        package default (ops.PRECISION).  Passed explicitly to every launch: the module keeps no launch state.
+        taps: a dict that receives clones of the fp32 token planes, each [B, E_i, gh_i, gw_i], at four points of stage i:
+        'embed{i}' (after the patch-embed LayerNorm), 'block{i}.0', 'peg{i}', 'block{i}.1' (tests; nothing else is launched differently)."""
         from . import ops
         from .ops import EPI_GELU, EPI_NONE, EPI_RES, Planes
         prec = ops.PRECISION if precision is None else (ops._PRECISION_NAMES[precision] if isinstance(precision, str) else int(precision))
@@ -171,8 +173,15 @@ class Twins_CSC(nn.Module):
             # image, exactly as in the refinement loop; the fp32-class modes keep fp32 planes throughout
             handover = prec in (ops.PRECISION_F16X2, ops.PRECISION_F16) and (T * H * W) % 256 == 0 and self.koct_handover
 
-            def newk(rows, n):
-                if not handover:
+            # the exact VALU attention cores read and write fp32 planes only: their qkv input and output are never k-octets
+            attn_koct = not self.exact_attention
+
+            def tap(name, X):
+                if taps is not None:
+                    taps[name] = X.tensor().view(B, X.rows, gh, gw).clone()
+
+            def newk(rows, n, koct=True):
+                if not (handover and koct):
                     return new(rows, n)
                 assert rows % 8 == 0
                 return Planes(torch.empty(B * rows * n // 2, dtype=torch.float32, device=dev), 0, rows * n, B, rows, n,
@@ -199,28 +208,32 @@ class Twins_CSC(nn.Module):
                 gh, gw = gh // k, gw // k
                 N = gh * gw
                 tok = ln(lin(f"patch_embeds.{i}.proj", Planes.of(_im2col(grid, k))), f"patch_embeds.{i}.norm")
+                tap(f"embed{i}", tok)
                 # block 0: locally grouped (7x7 window) attention + MLP, both residual
                 b0 = f"blocks.{i}.0"
-                qkv = lin(b0 + ".attn.qkv", ln(tok, b0 + ".norm1", koct=True), koct=True)
-                att = newk(E, N)
+                qkv = lin(b0 + ".attn.qkv", ln(tok, b0 + ".norm1", koct=True), koct=attn_koct)
+                att = newk(E, N, attn_koct)
                 ops.window_attn(qkv, pk["qkv_bias"][i], att, heads, gh, gw, self.WS, cx=cx0, exact=self.exact_attention)
                 tok = lin(b0 + ".attn.proj", att, EPI_RES, R=tok)
                 tok = lin(b0 + ".mlp.fc2", lin(b0 + ".mlp.fc1", ln(tok, b0 + ".norm2", koct=True), EPI_GELU, koct=True), EPI_RES, R=tok)
+                tap(f"block{i}.0", tok)
                 # positional conv after the first block (twins_csc.py:73-74)
                 pw, pb = pk[f"pos_block.{i}.proj.0"]
                 peg = new(E, N)
                 ops.dwconv3x3_res(tok, pw, pb, peg, gh, gw)
                 tok = peg
+                tap(f"peg{i}", tok)
                 # block 1: global sub-sampled attention + MLP
                 b1 = f"blocks.{i}.1"
                 y = ln(tok, b1 + ".norm1")
                 q = lin(b1 + ".attn.q", y)
                 s = lin(b1 + ".attn.sr", Planes.of(_im2col(y.tensor().view(B, E, gh, gw), sr)))
                 kv = lin(b1 + ".attn.kv", ln(s, b1 + ".attn.norm"))
-                att = newk(E, N)
+                att = newk(E, N, attn_koct)
                 ops.subsample_attn(q, kv, att, heads, cx=cx0, exact=self.exact_attention)
                 tok = lin(b1 + ".attn.proj", att, EPI_RES, R=tok)
                 tok = lin(b1 + ".mlp.fc2", lin(b1 + ".mlp.fc1", ln(tok, b1 + ".norm2", koct=True), EPI_GELU, koct=True), EPI_RES, R=tok)
+                tap(f"block{i}.1", tok)
                 grid = tok.tensor().view(B, E, gh, gw)
             h, w = H // 8, W // 8
             return grid.view(B, self.DIMS[1], T, h, w).permute(0, 2, 1, 3, 4).contiguous()
