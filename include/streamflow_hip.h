@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 136
+#define SF_VERSION 137
 
 enum {
     SF_OK = 0,
@@ -410,6 +410,9 @@ int sf_gma_flash_project_v(void* ws, int64_t ws_bytes, const void* x_koct, int64
  * image, an opaque format between the two calls below) -- and every iteration only streams them past v:
  * half the matrix-core work, no exponentials, HBM-bound (n_img * Ppad^2 * 2 bytes per iteration, Ppad = P rounded up to 128).
  *   sf_gma_stored_p_bytes: size of `pbuf` (caller-owned, 16-byte aligned, persists over the clip's iterations).
+ *   sf_gma_stored_image_ok: 1 when an image of P pixels can be stored at all, 0 otherwise: sf_gma_flash_store_p and
+ *       sf_gma_stored_aggregate refuse an image whose stored weights (Ppad^2 * 2 bytes plus the read-ahead) reach 4 GiB or whose
+ *       packed planes reach 1 GiB, whatever n_img is.  A caller sizes with both: the total with _p_bytes, each image with this.
  *   sf_gma_flash_store_p: once per clip, after sf_gma_flash_pack_qk(stats_qk_products = qk_products): writes pbuf.
  *   sf_gma_stored_aggregate: every iteration; out = mf + gamma / rowsum * v P^T.  v as in sf_gma_flash_aggregate (v_f16 = 1: fp16
  *       rows; v == NULL: the v planes of ws are current, sf_gma_flash_project_v).  With the same ws the result is bit-identical to
@@ -418,6 +421,7 @@ int sf_gma_flash_project_v(void* ws, int64_t ws_bytes, const void* x_koct, int64
  *   header of ws only; sf_gma_stored_aggregate without a store_p behind the last pack_qk, after a pack_qk for another P or with
  *   stats_qk_products = 0, gives NaN in every element of out and out_koct -- split and unsplit key range alike. */
 int64_t sf_gma_stored_p_bytes(int n_img, int P);
+int sf_gma_stored_image_ok(int P);
 int sf_gma_flash_store_p(void* ws, int64_t ws_bytes, void* pbuf, int64_t pbuf_bytes, int n_img, int P, int qk_products,
                          void* stream);
 int sf_gma_stored_aggregate(void* ws, int64_t ws_bytes, const void* pbuf, int64_t pbuf_bytes, const void* v, int v_f16,

@@ -157,6 +157,7 @@ SIGNATURES = {
     "sf_gma_flash_aggregate_f16v": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sf_gma_flash_project_v": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _f, _i, _i, _i, _vp]),
     "sf_gma_stored_p_bytes": (_i64, [_i, _i]),
+    "sf_gma_stored_image_ok": (_i, [_i]),
     "sf_gma_flash_store_p": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp]),
     "sf_gma_stored_aggregate": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _vp]),
     "sf_ffn_pair": (_i, [C.POINTER(SfFfnPair), _vp]),
@@ -242,7 +243,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 136:
+    if lib.sf_version() < 137:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -945,6 +945,14 @@ extern "C" int64_t sf_gma_stored_p_bytes(int n_img, int P) {
     return (int64_t)n_img * Ppad * Ppad * 2;
 }
 
+// The per-image rule of the two entry points below: the kernels address one image's packed planes with 31-bit and its stored weights
+// (with the read-ahead of three key tiles) with 32-bit byte offsets.  1 = an image of P pixels is accepted, 0 = refused.
+extern "C" int sf_gma_stored_image_ok(int P) {
+    if (P <= 0) return 0;
+    const int64_t Ppad = sf::ceil_div(P, BQ) * BQ;
+    return 2 * plane_bytes((int)Ppad) < ((int64_t)1 << 31) && Ppad * Ppad * 2 + 3 * (Ppad / 32) * 4096 < ((int64_t)1 << 32);
+}
+
 extern "C" int sf_gma_flash_store_p(void* ws, int64_t ws_bytes, void* pbuf, int64_t pbuf_bytes, int n_img, int P, int qk_products,
                                     void* stream) {
     SF_REQUIRE(ws && pbuf, "sf_gma_flash_store_p: null pointer");
@@ -955,7 +963,7 @@ extern "C" int sf_gma_flash_store_p(void* ws, int64_t ws_bytes, void* pbuf, int6
     SF_REQUIRE(pbuf_bytes >= sf_gma_stored_p_bytes(n_img, P) && (reinterpret_cast<uintptr_t>(pbuf) & 15) == 0,
                "sf_gma_flash_store_p: pbuf must hold sf_gma_stored_p_bytes(n_img, P) bytes, 16-byte aligned");
     const int Ppad = sf::ceil_div(P, BQ) * BQ;
-    SF_REQUIRE(2 * plane_bytes(Ppad) < ((int64_t)1 << 31) && (int64_t)Ppad * Ppad * 2 + 3 * (int64_t)(Ppad / 32) * 4096 < ((int64_t)1 << 32),
+    SF_REQUIRE(sf_gma_stored_image_ok(P),
                "sf_gma_flash_store_p: image too large (the stored weights of one image must stay under 4 GiB)");
     FlashArgs g = {};
     g.ws = (const char*)ws; g.P = P; g.Ppad = Ppad; g.nsplit = 1;
@@ -983,7 +991,7 @@ extern "C" int sf_gma_stored_aggregate(void* ws, int64_t ws_bytes, const void* p
     SF_REQUIRE(pbuf_bytes >= sf_gma_stored_p_bytes(n_img, P) && (reinterpret_cast<uintptr_t>(pbuf) & 15) == 0,
                "sf_gma_stored_aggregate: pbuf must hold sf_gma_stored_p_bytes(n_img, P) bytes, 16-byte aligned");
     const int Ppad = sf::ceil_div(P, BQ) * BQ;
-    SF_REQUIRE(2 * plane_bytes(Ppad) < ((int64_t)1 << 31) && (int64_t)Ppad * Ppad * 2 + 3 * (int64_t)(Ppad / 32) * 4096 < ((int64_t)1 << 32),
+    SF_REQUIRE(sf_gma_stored_image_ok(P),
                "sf_gma_stored_aggregate: image too large (the stored weights of one image must stay under 4 GiB)");
     if (!v) {}                                                // the v planes of ws are current (sf_gma_flash_project_v)
     else if (v_f16)

@@ -336,8 +336,9 @@ class GmaPlan:
 def resolve_gma(gma_mode: str, precision: int, flash_qk_products: int, options: EngineOptions, n_img: int, P: int,
                 project_ok: bool) -> GmaPlan:
     """The GMA form of a plan over n_img images of P pixels.  project_ok: the fused v projection can run (fp16 activations, k-octet
-    copies active for this grid, to_v 128 x 128 without bias).  Host arithmetic and the library's sizing functions only.
-    (The stored weights' limit of 4 GiB per image, a rule of attn.hip, belongs here once the library exports it.)"""
+    copies active for this grid, to_v 128 x 128 without bias).  Host arithmetic and the library's sizing functions only: the total size of
+    the stored weights (gma_stored_p_bytes against the options' limits) and attn.hip's rule for ONE image (gma_stored_image_ok: under
+    4 GiB) -- a grid whose single image would be refused by the store / aggregate entry points runs the fused recompute instead."""
     split = precision != ops.PRECISION_FP32
     fused = gma_mode in ("flash", "stored", "hybrid")
     if fused and not split:
@@ -355,7 +356,7 @@ def resolve_gma(gma_mode: str, precision: int, flash_qk_products: int, options: 
     # (same results; the measurements are at EngineOptions.stored_auto_px)
     auto_stored = (gma_mode == "flash" and int(options.stored_auto_px) > 0 and
                    (P >= int(options.stored_auto_px) or flash_qk_products >= 2) and
-                   ops.gma_stored_p_bytes(n_img, P) <= (int(options.stored_auto_max_gb) << 30))
+                   ops.gma_stored_image_ok(P) and ops.gma_stored_p_bytes(n_img, P) <= (int(options.stored_auto_max_gb) << 30))
     whole = gma_mode == "stored" or auto_stored
     # 'hybrid': stored weights (HBM-bound) and recompute (power-bound) side by side on disjoint images.  Both
     # halves read the projected v, and neither may be small enough for the key-split form -- else the recompute kernel runs alone
@@ -363,7 +364,7 @@ def resolve_gma(gma_mode: str, precision: int, flash_qk_products: int, options: 
     project_v = bool(options.project_v and project_ok)
     halves_ok = lambda: project_v and ops.gma_no_key_split(n_store, P) and ops.gma_no_key_split(n_img - n_store, P)
     if not ((whole or gma_mode == "hybrid") and options.flash_stats and n_store > 0 and (n_store == n_img or halves_ok()) and
-            ops.gma_stored_p_bytes(n_store, P) <= (int(options.stored_p_max_gb) << 30)):
+            ops.gma_stored_image_ok(P) and ops.gma_stored_p_bytes(n_store, P) <= (int(options.stored_p_max_gb) << 30)):
         n_store = 0
     form = "recompute" if n_store == 0 else ("stored" if n_store == n_img else "hybrid")
     return GmaPlan(form, 1, False, ks, n_store, project_v, bool(auto_stored and n_store > 0))
@@ -481,6 +482,36 @@ class _Plan:
         pit = self.corr_pitch[l] if self.corr_pitch else wl
         return self.lvls[l].view(self.Pn, self.Bc * self.P, hl, pit)[..., :wl]
 
+    TAPS = ("nets0", "inps", "qk", "volume",                                            # current after the setup (forward(iters=0))
+            "corr", "f128", "cor256", "cat256", "mf", "mft", "mfg", "nets", "delta", "flow", "coords1", "m256", "mask", "up")
+
+    def taps(self, names: Optional[Sequence[str]] = None, cpu: bool = True) -> Dict[str, object]:
+        """Tests only, read-only: fp32 CLONES of the named plan buffers as they stand after a forward (eager or replayed), each
+        [n, rows, h, w]; k-octet-only and fp16 buffers through Planes.tensor().  'volume': the four level_maps, image-major
+        [n, P, h_l, w_l]; 'nets0' = 'nets'
+        (the hidden state the setup wrote, before an iteration overwrites it); 'mf': rows 0 .. 125 (the flow rows belong to
+        flow_update); 'mask' is only written when mask.2 runs as a launch of its own (all_masks=True), 'up' is the [n, 2, 8h, 8w]
+        result.  Nothing here runs during a forward: the launch sequence does not know that it is observed."""
+        torch.cuda.synchronize(self.up.device)
+        out: Dict[str, object] = {}
+        for nm in (names or self.TAPS):
+            if nm not in self.TAPS:
+                raise RuntimeError(f"unknown tap {nm!r} (have {self.TAPS})")
+            if nm == "volume":
+                t = [self.level_maps(l).float().reshape(self.Pn, self.Bc, self.P, self.h >> l, self.w >> l).transpose(0, 1)
+                     .reshape(self.n, self.P, self.h >> l, self.w >> l).clone() for l in range(4)]           # image = clip * pairs + pair
+                out[nm] = [v.cpu() for v in t] if cpu else t
+                continue
+            if nm == "up":
+                t = self.up.clone()
+            else:
+                X = replace(getattr(self, "nets" if nm == "nets0" else nm), shadow=None)
+                if nm == "mf":
+                    X = X.slice(0, HDIM - 2)
+                t = X.tensor().float().clone().contiguous().view(self.n, X.rows, self.h, self.w)
+            out[nm] = t.cpu() if cpu else t
+        return out
+
 
 class HotPathEngine:
     """`forward(fmaps, cnets, iters)` == reference loop in test_mode (streamflow.py:110-147)."""
@@ -492,8 +523,10 @@ class HotPathEngine:
         """precision: 'f16x3' (split fp16, fp32-class accuracy, default), 'fp32' (exact fp32 MFMA), 'f16x2'
         (weights split, activations rounded to fp16: ~1e-4 px EPE, faster) or 'f16' (weights and activations fp16);
         None = the package-wide setting (streamflow_amd.ops.PRECISION).
-        corr_dtype: 'f32' keeps the correlation pyramids in fp32 as the reference does (corr.py:13, arithmetic =
-        `precision`); 'f16' stores them as fp16 and builds them with single f16 MFMA products (SF_PRECISION_F16).
+        corr_dtype: 'f32' keeps the correlation pyramids in fp32 as the reference does (corr.py:13).  Their arithmetic: under
+        'fp32' exact fp32 MFMA products into row-major maps (sf_corr_build_pyramid); under every split precision three split-fp16
+        products (fp32-class), into cache-line blocks (options.corr_blocked32, sf_corr_build_blocked32) or row-major maps.
+        'f16' stores them as fp16 and builds them with single f16 MFMA products (SF_PRECISION_F16).
         gma_mode: 'matrix' = attention matrix materialised once per clip (gma.py), 'flash' = fused recompute kernel every
         iteration (demo.py:235-258), 'stored' = the fused kernel's own softmax weights stored once per clip as fp16 in fragment
         order and streamed every iteration (bit-identical to 'flash'; n_img * Ppad^2 * 2 bytes, options.stored_p_max_gb),
@@ -510,7 +543,9 @@ class HotPathEngine:
         # fp16 volumes in the blocked layout (+ k-octet-only hand-over of the correlation features) wherever the f16x2 / f16
         # hand-over formats are active; options.corr_blocked = False keeps the row-major fp16 volumes
         self.corr_blocked = self.corr_f16 and self.options.corr_blocked
-        self.corr_blocked32 = (not self.corr_f16) and self.options.corr_blocked32
+        # blocked fp32 volumes are built from split-fp16 products (csrc/corr_blocked32.hip): fp32-class, not the exact fp32 MFMA that
+        # precision='fp32' promises -- that precision keeps the row-major maps of sf_corr_build_pyramid at SF_PRECISION_FP32
+        self.corr_blocked32 = (not self.corr_f16) and self.options.corr_blocked32 and self.precision != ops.PRECISION_FP32
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("HotPathEngine needs an MI355X device (cuda:N); there is no CPU fallback")
@@ -566,11 +601,12 @@ class HotPathEngine:
         gma = resolve_gma(self.gma_mode, self.precision, self.flash_qk_products, self.options, Bc * self.W.pairs, h * w,
                           project_ok=shadows and self.W.to_v.M == self.W.to_v.K == HDIM and self.W.to_v.bias is None)
         pl = self._plans.pop(key, None)
-        if pl is None or pl.gma != gma:                              # (a mode or precision assigned after the plan was made)
+        blocked32 = bool(self.corr_blocked32 and self.precision != ops.PRECISION_FP32)     # (exact fp32: never the split-fp16 blocked build)
+        if pl is None or pl.gma != gma or pl.corr_blocked32 != blocked32:   # (a mode or precision assigned after the plan was made)
             while len(self._plans) >= max(1, self.max_plans):
                 self._plans.pop(next(iter(self._plans)))            # dicts keep insertion order: first = oldest
             pl = _Plan(self.W, Bc, h, w, D, self.device, gma, corr_f16=self.corr_f16, shadows=shadows,
-                       corr_blocked=self.corr_blocked, corr_blocked32=self.corr_blocked32,
+                       corr_blocked=self.corr_blocked, corr_blocked32=blocked32,
                        koct_io=self.options.koct_io and self.options.hidden_koct)   # (k-octet-only blocks need k-octet producers)
         self._plans[key] = pl                                        # (re)insert as most recent
         return pl

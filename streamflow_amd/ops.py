@@ -1099,6 +1099,11 @@ def gma_stored_p_bytes(n_img: int, P: int) -> int:
     return int(_lib.load().sf_gma_stored_p_bytes(n_img, P))
 
 
+def gma_stored_image_ok(P: int) -> bool:
+    """One image of P pixels is within what gma_flash_store_p / gma_stored_aggregate accept (under 4 GiB of stored weights)."""
+    return bool(_lib.load().sf_gma_stored_image_ok(P))
+
+
 @on_tensor_device
 def gma_flash_store_p(ws: torch.Tensor, pbuf: torch.Tensor, n_img: int, P: int, qk_products: int, cx: Optional[Ctx] = None) -> None:
     """Once per clip, after gma_flash_pack_qk(stats_qk_products=qk_products): the softmax weights of every (query, key) as fp16 in

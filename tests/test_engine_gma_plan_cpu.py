@@ -104,3 +104,33 @@ def test_the_form_is_a_function_of_its_arguments_only():
     a = resolve_gma("hybrid", SPLIT, 1, o, 18, 7040, True)
     assert a == resolve_gma("hybrid", SPLIT, 1, replace(o, split_solo=0, parallel_branches=False), 18, 7040, True)
     assert hash(a) == hash(resolve_gma("hybrid", SPLIT, 1, o, 18, 7040, True))
+
+
+SWEEP_P = (16384, 32400, 46000, 46400, 57600, 92160)
+
+
+def test_the_library_accepts_every_image_the_plan_stores(lib):
+    """attn.hip refuses a single image whose stored weights reach 4 GiB (sf_gma_stored_image_ok), whatever the total: whenever a
+    plan stores anything, the exported rule accepts its grid -- and a grid it refuses resolves to the recompute form.  (2, 57600)
+    is 13.3 GB in all, under every total limit, and 6.6 GB per image: the stored form it used to get raised in the setup."""
+    assert [bool(lib.sf_gma_stored_image_ok(P)) for P in SWEEP_P] == [True, True, True, False, False, False]
+    assert not lib.sf_gma_stored_image_ok(0) and not lib.sf_gma_stored_image_ok(-5) and lib.sf_gma_stored_image_ok(1)
+    for P in (46208, 46209):                                                    # Ppad = 46208 is the last padded size under the limit
+        Ppad = -(-P // 128) * 128
+        assert bool(lib.sf_gma_stored_image_ok(P)) == (Ppad * Ppad * 2 + 3 * (Ppad // 32) * 4096 < 1 << 32) == (P == 46208)
+    seen = set()
+    for P in SWEEP_P:
+        for n in (1, 2, 3):
+            for mode in FUSED_MODES:
+                for products in (1, 3):
+                    g = resolve(mode, n, P, products=products)
+                    if g.n_store > 0:
+                        assert lib.sf_gma_stored_image_ok(P), (mode, n, P, products, g)
+                        assert ops.gma_stored_p_bytes(g.n_store, P) <= 64 << 30
+                    else:
+                        assert (g.form, g.auto_stored) == ("recompute", False)
+                    if not lib.sf_gma_stored_image_ok(P):
+                        assert (g.form, g.n_store, g.auto_stored) == ("recompute", 0, False), (mode, n, P, products)
+                        seen.add((n, P))
+    assert ops.gma_stored_p_bytes(2, 57600) <= 16 << 30 and (2, 57600) in seen
+    assert resolve("flash", 2, 46000).form == "stored" and resolve("stored", 1, 46000).n_store == 1     # still stored below the limit

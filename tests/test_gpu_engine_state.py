@@ -189,6 +189,7 @@ def test_configurations_take_the_paths_they_are_named_for(dev):
     assert pl["config2_stored", GRID_A].pbuf is not None and pl["config2_fp16", GRID_A].pbuf is None
     for c in ("fp32", "f16x3_matrix"):
         assert not pl[c, GRID_A].flash and pl[c, GRID_A].attn_rows == P_a and pl[c, GRID_B].attn_rows == P_b
+    assert not pl["fp32", GRID_A].corr_blocked32 and pl["fp32", GRID_A].lvls is not None       # exact fp32: the row-major build
     assert pl["fp32", GRID_A].attn16 is None and pl["f16x3_matrix", GRID_A].attn16 is not None and pl["f16x3_matrix", GRID_B].attn16 is None
     assert pl["config2_rows", GRID_A].shadows and not pl["config2_rows", GRID_A].corr_blocked and pl["config2_rows", GRID_A].lvls is not None
     assert pl["config2_rows", GRID_A].corr.shadow is not None
