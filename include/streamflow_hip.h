@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 137
+#define SF_VERSION 138
 
 enum {
     SF_OK = 0,
@@ -914,6 +914,70 @@ int sf_warp_frames(const uint8_t* src, int64_t src_frame_stride, int64_t src_row
                    uint8_t* out, const uint8_t* cls, uint8_t code_visible, const uint8_t* ref, int64_t ref_frame_stride,
                    int64_t ref_row_stride, int64_t ref_px_stride, int64_t ref_ch_stride, double* stats, void* ws, int64_t ws_bytes,
                    void* stream);
+
+/* ---- frame interpolation: forward splatting with integer weights, a batch of frame pairs per call --------------------------------
+ * sf_frame_interp: for n pairs of one size h x w the frame at time t = num / den (0 < num < den <= 64) between frame A (the frames
+ *   j, time 0) and frame B (the frames j + 1, time 1).  A, B: uint8 with 3 channels, byte (i, y, x, ch) at a + i a_frame_stride +
+ *   y a_row_stride + x a_px_stride + ch a_ch_stride (bytes, >= 0, as sf_warp_frames' src; b likewise with its own strides).  fwd: the
+ *   flows A -> B, bwd: the flows B -> A, fp32 planes addressed as sf_flow_consistency's.  cls_f / cls_b: optional, together: the class
+ *   maps uint8 [n][h][w] sf_flow_consistency wrote for (fwd, bwd) and for (bwd, fwd); code_visible / code_occluded are the bytes that
+ *   mean visible / occluded there.  imp_vis, imp_occ, imp_other: integer importances 1 .. 16 of a source pixel whose class byte is
+ *   code_visible / code_occluded / anything else; without class maps every source pixel has imp_vis.
+ *
+ *   Splat, for side A with flow = fwd, ts = (float)num / (float)den, and for side B with flow = bwd, ts = (float)(den - num) /
+ *   (float)den (both quotients computed in fp32 on the host).  Source pixel (x, y) of a side with flow (u, v), fp32, every
+ *   operation rounded on its own:
+ *     px = (float)x + ts * u,  py = (float)y + ts * v,
+ *     the pixel contributes only if  px > -1 && px < (float)w && py > -1 && py < (float)h   (false for NaN, +-Inf, 1e30; made BEFORE
+ *       any conversion to an integer, so such flows never form an address),
+ *     x0 = (int)floorf(px), fx = px - floorf(px), wx1 = (int)floorf(fx * 64 + 0.5f) in 0 .. 64, wx0 = 64 - wx1; likewise y0, wy0, wy1,
+ *     tap (x0 + a, y0 + b), a, b in {0, 1}, has the integer weight wt = wxa * wyb (the four sum to exactly 4096) and contributes only
+ *       if wt != 0 and its position lies inside [0, w) x [0, h):
+ *         W += wt * imp,   C[ch] += wt * imp * byte[ch]      in the tap's four unsigned 64-bit accumulators of this side.
+ *   Integer sums do not depend on the order of arrival: the result is bitwise reproducible from run to run and for any grid.  (2^30
+ *   source pixels of the largest weight, importance and byte on one target sum to less than 2^54.)
+ *   Resolve, per target pixel, integer division throughout; every byte is the exact rational value rounded ONCE, half up (<= 255).
+ *   A side is present if its W > 0.  Only A / only B: out = (2 C[ch] + W) / (2 W) of that side, cover 1 / 2.  Both present, cover
+ *   0: with N = (den - num) CA[ch] WB + num CB[ch] WA and D = den WA WB (up to 2^108: 128-bit products),
+ *   out = (2 N + D) / (2 D) -- the blend of the two means as ONE quotient; the sides are not rounded to bytes first, which would
+ *   round twice and leave the byte up to a whole level from the real-valued result.  Neither (a hole), cover 3:
+ *   out = (a (den - num) + b num + den / 2) / den of the co-located bytes a, b of A and B.
+ *   out:   uint8 [n][h][w][3] dense.   cover: optional uint8 [n][h][w] dense, the codes above.
+ *   stats: fp64 [n][SF_INTERP_LEN] on the device; row i is ADDED to: PIXELS, then the pixels of each cover code (BOTH, A_ONLY, B_ONLY,
+ *          HOLES); exact counts.
+ *   ws:    sf_frame_interp_ws_bytes(n, h, w) = 2 * 4 * 8 * n * h * w bytes of accumulators (planar: uint64 [n][side][W, C0, C1,
+ *          C2][h][w]) plus the per-block partial rows of the stats; cleared by the call itself, not read by later calls.
+ *   Launches: a memset of the accumulators on the stream, the splat (grid: blocks per pair x n x 2 sides; a wave owns 256 consecutive
+ *   pixels of a row, lane l the pixels l + 64 j, so for smooth flows an atomic wave-instruction covers 512 contiguous bytes; plain
+ *   no-return 64-bit integer atomic adds in global memory, at most 128 added bytes per source pixel and side), the resolve (blocks
+ *   per pair x n) and the stats finish (a block per pair sums the partials in a fixed order).  The grid depends on (n, h, w) alone.
+ *   Enqueued on `stream`, no host synchronisation.
+ *   SF_ERR_BAD_ARG before any launch for: a null a, b, fwd, bwd, out, stats or ws; cls_f without cls_b or the reverse; h, w <= 0,
+ *   h * w >= 2^30, n outside 1 .. 65535; num, den outside 0 < num < den <= 64; a flow row stride < w, a zero channel stride, negative
+ *   field / byte strides; an importance outside 1 .. 16; flow pointers not 4-byte, stats / ws not 8-byte aligned; ws_bytes too small.
+ *   sf_frame_interp_ws_bytes returns SF_ERR_BAD_ARG for n, h, w outside the limits.
+ * sf_frame_interp_phases: the same call restricted to the launches named by `phases`, a mask of 1 = clear, 2 = splat, 4 = resolve
+ *   and finish (7 = sf_frame_interp); for timing the parts (tools/frame_interp_bench.py).  The exception to the workspace rule
+ *   above: without the clear (bit 1) the splat ADDS to whatever the accumulators in `ws` hold, and without the splat the resolve
+ *   reads what earlier calls left there, so the caller must keep `ws`, n, h and w unchanged between the calls of one sequence, and
+ *   only the sequence clear, splat, resolve (in one call or several) gives sf_frame_interp's result. */
+enum {
+    SF_INTERP_PIXELS = 0, SF_INTERP_BOTH = 1, SF_INTERP_A_ONLY = 2, SF_INTERP_B_ONLY = 3, SF_INTERP_HOLES = 4, SF_INTERP_LEN = 5
+};
+int64_t sf_frame_interp_ws_bytes(int n, int h, int w);
+int sf_frame_interp(const uint8_t* a, int64_t a_frame_stride, int64_t a_row_stride, int64_t a_px_stride, int64_t a_ch_stride,
+                    const uint8_t* b, int64_t b_frame_stride, int64_t b_row_stride, int64_t b_px_stride, int64_t b_ch_stride,
+                    const float* fwd, int64_t fwd_field_stride, int64_t fwd_ch_stride, int64_t fwd_row_stride, const float* bwd,
+                    int64_t bwd_field_stride, int64_t bwd_ch_stride, int64_t bwd_row_stride, int n, int h, int w, int num, int den,
+                    const uint8_t* cls_f, const uint8_t* cls_b, uint8_t code_visible, uint8_t code_occluded, int imp_vis, int imp_occ,
+                    int imp_other, uint8_t* out, uint8_t* cover, double* stats, void* ws, int64_t ws_bytes, void* stream);
+int sf_frame_interp_phases(const uint8_t* a, int64_t a_frame_stride, int64_t a_row_stride, int64_t a_px_stride, int64_t a_ch_stride,
+                           const uint8_t* b, int64_t b_frame_stride, int64_t b_row_stride, int64_t b_px_stride, int64_t b_ch_stride,
+                           const float* fwd, int64_t fwd_field_stride, int64_t fwd_ch_stride, int64_t fwd_row_stride,
+                           const float* bwd, int64_t bwd_field_stride, int64_t bwd_ch_stride, int64_t bwd_row_stride, int n, int h,
+                           int w, int num, int den, const uint8_t* cls_f, const uint8_t* cls_b, uint8_t code_visible,
+                           uint8_t code_occluded, int imp_vis, int imp_occ, int imp_other, uint8_t* out, uint8_t* cover, double* stats,
+                           void* ws, int64_t ws_bytes, int phases, void* stream);
 
 /* ---- PNG frames: row unfiltering of inflated IDAT streams (PNG specification, section 9; flow_io.read_png on the host) ----------
  * The host inflates (zlib); the device undoes the row filters of a whole batch of equally shaped images in one launch, so the

@@ -199,6 +199,11 @@ SIGNATURES = {
     "sf_warp_frames_ws_bytes": (_i64, [_i, _i, _i]),
     "sf_warp_frames": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, C.c_uint8, _vp, _i64, _i64, _i64,
                             _i64, _vp, _vp, _i64, _vp]),
+    "sf_frame_interp_ws_bytes": (_i64, [_i, _i, _i]),
+    "sf_frame_interp": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i,
+                             _i, _i, _vp, _vp, C.c_uint8, C.c_uint8, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sf_frame_interp_phases": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i,
+                                    _i, _i, _i, _i, _vp, _vp, C.c_uint8, C.c_uint8, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
     "sf_frames_to_clips": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_clips_to_flows": (_i, [C.POINTER(SfPairPtrs), _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sf_png_unfilter": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp]),
@@ -243,7 +248,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 137:
+    if lib.sf_version() < 138:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

@@ -5,8 +5,8 @@ The check is the one of Sundaram et al. 2010 with the constants of UnFlow (Meist
 backward flow, sampled where the forward flow points, leads back to within  |f + b|^2 <= alpha (|f|^2 + |b|^2) + beta;  the constants
 are theirs (0.01, 0.5), not tuned here.  Everything per pixel is the two kernels of csrc/flow_consistency.hip
 (ops.flow_consistency, ops.warp_frames), a whole batch of pairs per call; the backward flows come from
-video.predict_video(..., bidirectional=True).  Out of scope: forward splatting, frame interpolation, and scoring the masks against
-ground-truth occlusion maps.
+video.predict_video(..., bidirectional=True); streamflow_amd.interpolate splats frames in between along the same flows.  Out of
+scope: scoring the masks against ground-truth occlusion maps.
 """
 from __future__ import annotations
 

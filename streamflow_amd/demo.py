@@ -161,7 +161,8 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                   save_dir: str = None, flo_dir: str = None, rad_max=None, png_decode: str = "host",
                                   png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90,
                                   jpeg_split: str = "auto", bidirectional: bool = False, occlusion_dir: str = None,
-                                  warp_dir: str = None, report: bool = False) -> int:
+                                  warp_dir: str = None, report: bool = False, interpolate: int = None, slowmo_dir: str = None,
+                                  slowmo_video: str = None) -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
     baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
@@ -177,7 +178,12 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     ``frame_%04d_bwd.flo``.  occlusion_dir: the forward-backward consistency classes of every pair as 8-bit grey
     ``frame_%04d.png`` (255 visible, 0 occluded, 128 outside the frame; consistency.MASK_CODES), written where `png_encode` says.
     warp_dir: frame j + 1 warped onto frame j as RGB ``frame_%04d.png``.  report: consistency.video_report's lines are printed at
-    the end.  The last three imply bidirectional; without any of them nothing changes."""
+    the end.  The last three imply bidirectional; without any of them nothing changes.
+
+    interpolate: an integer factor 2 .. 64: the video with `interpolate` times as many frames (streamflow_amd.interpolate: forward
+    splatting along both flows, interpolate - 1 frames between every two; implies bidirectional), written as
+    ``slowmo_dir/slow_%06d.png`` (where `png_encode` says) and / or as one Motion-JPEG AVI file `slowmo_video` (`fps`,
+    `jpeg_quality`); the input frames are passed through.  With `report` one more line gives the shares of the cover codes."""
     import os
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
@@ -187,12 +193,14 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
     model = StreamFlowT4(ckpt).to(device).eval()
-    bidirectional = bool(bidirectional or occlusion_dir or warp_dir or report)
-    for d in (save_dir, flo_dir, occlusion_dir, warp_dir):
+    if (interpolate is None) != (not slowmo_dir and not slowmo_video):
+        raise ValueError("read_frames_and_group_predict: `interpolate` and a slow-motion output (slowmo_dir, slowmo_video) come together")
+    bidirectional = bool(bidirectional or occlusion_dir or warp_dir or report or interpolate)
+    for d in (save_dir, flo_dir, occlusion_dir, warp_dir, slowmo_dir):
         if d:
             os.makedirs(d, exist_ok=True)
     written = [0]
-    if video_path:
+    if video_path or slowmo_video:
         jpeg_gpu.quant_tables(jpeg_quality)
     writer = []                                                          # opened by the first batch, which knows the frame size
 
@@ -230,6 +238,29 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
 
     from . import consistency
     reporter = consistency.ReportSink(then=then) if report else None
+    slow_writer = []
+
+    def emit_slow(first: int, images: torch.Tensor) -> None:
+        """The frames first .. of the slow-motion video, device uint8 [m, H, W, 3]."""
+        from . import png_gpu
+        if slowmo_dir:
+            paths = [os.path.join(slowmo_dir, "slow_%06d.png" % (first + k)) for k in range(images.shape[0])]
+            if png_encode == "gpu":
+                png_gpu.encode_batch(images.contiguous(), paths)
+            else:
+                host = images.cpu().numpy()
+                for k, p in enumerate(paths):
+                    flow_io.write_png(p, host[k])
+        if slowmo_video:
+            if not slow_writer:
+                slow_writer.append(avi.MjpegWriter(slowmo_video, int(images.shape[2]), int(images.shape[1]), fps))
+            for blob in jpeg_gpu.encode_batch(images.contiguous(), quality=jpeg_quality):
+                slow_writer[0].add(blob)
+
+    slow = None
+    if interpolate is not None:
+        from . import interpolate as interp
+        slow = interp.InterpSink(interpolate, emit_slow)
 
     def sink_both(first_pair: int, fwd: torch.Tensor, bwd: torch.Tensor, held: torch.Tensor) -> None:
         sink(first_pair, fwd)
@@ -244,6 +275,8 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
             cls = ops.flow_consistency(fwd, bwd, consistency.ALPHA, consistency.BETA, consistency.MASK_CODES)[0] if occlusion_dir else None
             warped = consistency.warp_back(held, fwd)[0] if warp_dir else None
             then(first_pair, fwd, bwd, held, (cls, None), (warped, None))
+        if slow is not None:
+            slow(first_pair, fwd, bwd, held)
 
     try:
         if bidirectional:
@@ -251,13 +284,17 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                 sink=sink_both, bidirectional=True)
         else:
             video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink)
+        if slow is not None:
+            slow.finish()
     finally:
-        if writer:
-            writer[0].close()
+        for wr in writer + slow_writer:
+            wr.close()
     if reporter is not None:
         rep = reporter.report()
         for name in consistency.DIRECTIONS:
             print(consistency.report_line(name, rep[name]))
+        if slow is not None:
+            print(interp.report_line(slow.report()))
     return written[0]
 
 
@@ -268,7 +305,7 @@ def arg_parser():
                                              "video and .flo files")
     ap.add_argument("--frames", required=True, help="directory of PNG frames or of baseline JPEG frames (sorted by name), or a Motion-JPEG .avi file")
     ap.add_argument("--ckpt", required=True, help="StreamFlow checkpoint")
-    ap.add_argument("--out", default=None, help="directory for frame_%%04d.png (may be left out only with --video)")
+    ap.add_argument("--out", default=None, help="directory for frame_%%04d.png (may be left out only with --video or a slow-motion output)")
     ap.add_argument("--video", default=None, help="one Motion-JPEG AVI file of the colour-wheel images, encoded on the GPU")
     ap.add_argument("--fps", type=float, default=8, help="frames per second of --video")
     ap.add_argument("--jpeg-quality", type=int, default=90, help="IJG quality 1 .. 100 of the frames of --video")
@@ -294,19 +331,39 @@ def arg_parser():
                     help="directory for frame j + 1 warped onto frame j, RGB frame_%%04d.png (implies --bidirectional)")
     ap.add_argument("--report", action="store_true",
                     help="print the consistency report of the video, one line per direction (implies --bidirectional)")
+
+    def factor(text: str) -> int:
+        try:
+            value = int(text)
+        except ValueError:
+            value = 0
+        if not 2 <= value <= 64:
+            raise argparse.ArgumentTypeError(f"an integer 2 .. 64, got {text!r}")
+        return value
+
+    ap.add_argument("--interpolate", type=factor, default=None, metavar="F",
+                    help="slow motion: F times as many frames (2 .. 64), F - 1 frames splatted between every two along both flows "
+                         "(implies --bidirectional; needs --slowmo and / or --slowmo-video)")
+    ap.add_argument("--slowmo", default=None, metavar="DIR", help="directory for the frames of the slow-motion video, slow_%%06d.png")
+    ap.add_argument("--slowmo-video", default=None, metavar="FILE.avi",
+                    help="the slow-motion video as one Motion-JPEG AVI file (--fps, --jpeg-quality), encoded on the GPU")
     return ap
 
 
 def main(argv=None) -> int:
     ap = arg_parser()
     a = ap.parse_args(argv)
-    if not a.out and not a.video:
+    slow_out = bool(a.slowmo or a.slowmo_video)
+    if not a.out and not a.video and not slow_out:
         ap.error("the following arguments are required: --out (or --video)")
+    if (a.interpolate is not None) != slow_out:
+        ap.error("--interpolate and a slow-motion output (--slowmo, --slowmo-video) come together")
     n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
                                       save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode,
                                       png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality, jpeg_split=a.jpeg_split,
-                                      bidirectional=a.bidirectional, occlusion_dir=a.occlusion, warp_dir=a.warp, report=a.report)
-    print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp) if d))
+                                      bidirectional=a.bidirectional, occlusion_dir=a.occlusion, warp_dir=a.warp, report=a.report,
+                                      interpolate=a.interpolate, slowmo_dir=a.slowmo, slowmo_video=a.slowmo_video)
+    print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp, a.slowmo, a.slowmo_video) if d))
     return 0
 
 

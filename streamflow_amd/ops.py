@@ -1553,7 +1553,74 @@ def warp_frames(src: torch.Tensor, flows: torch.Tensor, cls: Optional[torch.Tens
     return out, stats
 
 
-PNG_BPP = (1, 2, 3, 4, 6, 8)          # PNG filter distances sf_png_unfilter is built for: 8 / 16-bit grey, grey + alpha, RGB, RGBA
+INTERP_LEN = 5               # SF_INTERP_LEN: doubles per stats row of frame_interp
+INTERP_PIXELS, INTERP_BOTH, INTERP_A_ONLY, INTERP_B_ONLY, INTERP_HOLES = range(5)
+INTERP_MAX_DEN = 64
+
+
+@on_tensor_device
+def frame_interp(a: torch.Tensor, b: torch.Tensor, fwd: torch.Tensor, bwd: torch.Tensor, num: int, den: int, cls=None,
+                 importance: Sequence[int] = (16, 1, 16), cover: bool = False, stats: Optional[torch.Tensor] = None,
+                 codes: Sequence[int] = (0, 1), channels_last: Optional[bool] = None, max_ws_bytes: int = 1 << 30):
+    """The frames at time num / den (0 < num < den <= 64) between n frame pairs, by forward splatting with integer weights
+    (sf_frame_interp; include/streamflow_hip.h has the arithmetic): a, b uint8 [n, H, W, 3] or [n, 3, H, W] on the GPU, any strides
+    (as warp_frames; in a video a = frames[:-1], b = frames[1:]); fwd the flows a -> b, bwd the flows b -> a, fp32 [n, 2, H, W] with
+    contiguous rows.  cls: None or (cls_f, cls_b), flow_consistency's maps of (fwd, bwd) and of (bwd, fwd), uint8 [n, H, W]
+    contiguous, with codes = their bytes for (visible, occluded); importance = the integer weights 1 .. 16 of a (visible, occluded,
+    other) source pixel, the first for every pixel without cls.  Returns (out uint8 [n, H, W, 3], cover uint8 [n, H, W] or None:
+    0 both sides, 1 a only, 2 b only, 3 hole; stats float64 [n, INTERP_LEN], a given `stats` is ADDED to: INTERP_PIXELS and the
+    pixels of each cover code).  The workspace (64 bytes per pixel and pair) is allocated per call; the pairs are split into chunks so
+    that one call's workspace stays under `max_ws_bytes` (one pair at least).  The bytes do not depend on the chunking: all sums are
+    integer.  Enqueued on the current stream, no synchronisation."""
+    what = "frame_interp"
+    n, h, w = _flow_fields(fwd, "fwd", what)
+    dev = fwd.device
+    if _flow_fields(bwd, "bwd", what) != (n, h, w) or bwd.device != dev:
+        raise RuntimeError(f"{what}: fwd is {tuple(fwd.shape)} on {fwd.device}, bwd {tuple(bwd.shape)} on {bwd.device}")
+    sa = _frame_strides(a, "a", channels_last, (h, w), n, dev, what)
+    sb = _frame_strides(b, "b", channels_last, (h, w), n, dev, what)
+    num, den = int(num), int(den)
+    if not 0 < num < den <= INTERP_MAX_DEN:
+        raise RuntimeError(f"{what}: t = {num} / {den} (0 < num < den <= {INTERP_MAX_DEN})")
+    imp = tuple(int(v) for v in importance)
+    if len(imp) != 3 or any(not 1 <= v <= 16 for v in imp):
+        raise RuntimeError(f"{what}: importance must be three integers 1 .. 16 (visible, occluded, other), got {tuple(importance)}")
+    codes = tuple(int(c) for c in codes)
+    if len(codes) != 2 or any(not 0 <= c <= 255 for c in codes):
+        raise RuntimeError(f"{what}: codes must be two byte values (visible, occluded), got {codes}")
+    if cls is not None:
+        if not isinstance(cls, (tuple, list)) or len(cls) != 2:
+            raise RuntimeError(f"{what}: cls must be a pair (cls_f, cls_b) of class maps")
+        for c in cls:
+            if (not isinstance(c, torch.Tensor) or not c.is_cuda or c.device != dev or c.dtype != torch.uint8
+                    or tuple(c.shape) != (n, h, w) or not c.is_contiguous()):
+                raise RuntimeError(f"{what}: a class map must be contiguous uint8 [{n}, {h}, {w}] on {dev} (got "
+                                   f"{getattr(c, 'dtype', None)} {tuple(getattr(c, 'shape', ()))} on {getattr(c, 'device', None)}); "
+                                   "there is no CPU fallback")
+    stats = _stats_rows(stats, n, INTERP_LEN, dev, what)
+    lib = _lib.load()
+    per = int(lib.sf_frame_interp_ws_bytes(1, h, w))
+    if per < 0:
+        _lib.check(per, "sf_frame_interp_ws_bytes")
+    m = min(n, max(1, int(max_ws_bytes) // per))
+    while m > 1 and int(lib.sf_frame_interp_ws_bytes(m, h, w)) > int(max_ws_bytes):
+        m -= 1
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    cov = torch.empty(n, h, w, dtype=torch.uint8, device=dev) if cover else None
+    ws = torch.empty(int(lib.sf_frame_interp_ws_bytes(m, h, w)), dtype=torch.uint8, device=dev)
+    for lo in range(0, n, m):
+        k = min(m, n - lo)
+        _lib.check(lib.sf_frame_interp(a.data_ptr() + lo * sa[0], sa[0], sa[1], sa[2], sa[3], b.data_ptr() + lo * sb[0], sb[0], sb[1],
+                                       sb[2], sb[3], fwd[lo:].data_ptr(), fwd.stride(0), fwd.stride(1), fwd.stride(2),
+                                       bwd[lo:].data_ptr(), bwd.stride(0), bwd.stride(1), bwd.stride(2), k, h, w, num, den,
+                                       None if cls is None else cls[0][lo:].data_ptr(), None if cls is None else cls[1][lo:].data_ptr(),
+                                       codes[0], codes[1], imp[0], imp[1], imp[2], out[lo:].data_ptr(),
+                                       None if cov is None else cov[lo:].data_ptr(), stats[lo:].data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _lib.stream()), "sf_frame_interp")
+    return out, cov, stats
+
+
+PNG_BPP = (1, 2, 3, 4, 6, 8)         # PNG filter distances sf_png_unfilter is built for: 8 / 16-bit grey, grey + alpha, RGB, RGBA
 
 
 @on_tensor_device
