@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 138
+#define SF_VERSION 139
 
 enum {
     SF_OK = 0,
@@ -190,6 +190,43 @@ int sf_corr_build_blocked32(const float* f1, const float* f2, int64_t f_clip_str
                             void* ws, int64_t ws_bytes, void* stream);
 int sf_corr_lookup_blocked32(const void* vol, int64_t vol_img_stride_bytes, const float* coords, float* out,
                              int64_t out_img_stride, int B, int pairs, int h, int w, void* stream);
+
+/* ---- a1 + a2 + a3 WITHOUT a volume: on-demand lookup from packed features (core/corr.py:7-54; csrc/corr_direct.hip) -------
+ * Pooling is linear: level l of the volume at target cell J is <f1_i, pool_l(f2)_J> / sqrt(D), pool_l = the floor 2 x 2 mean
+ * applied l times to the features of frame 2.  Nothing of size N^2 is stored; every lookup computes the cells its windows touch.
+ *   sf_corr_direct_pack: once per clip; features addressed exactly as in sf_corr_build_blocked.  Writes, per image img = b*pairs + t
+ *       at ws + img * img_bytes, five REGIONS back to back: f1 (N = h*w cells), then level l = 0..3 of the pyramid of f2
+ *       (Nl = (h>>l)*(w>>l) cells, cell (y, x) at y*(w>>l) + x); img_bytes = parts * (Dp/8) * 16 * (2 N + N1 + N2 + N3).
+ *           region = [part][k-octet][cell][8] IEEE fp16, Dp = D rounded up to 32 (rows D .. Dp-1 zero),
+ *           parts = 1 (SF_PRECISION_F16: the value rounded to nearest) or 2 (SF_PRECISION_F16X3: hi, lo of split_operand.h split8()).
+ *       Levels 1..3 are pooled in fp32 from the fp32 level below (vertical pair, horizontal pair, times 0.25) and rounded to the
+ *       operand format ONCE.  Every frame is packed per side and pair (a frame shared by two pairs is packed twice: the result
+ *       is bitwise the same whichever way f2 is handed over).  Every byte of the workspace is written.
+ *   sf_corr_direct_ws_bytes: B * pairs * img_bytes -- exactly that many bytes suffice (0 for an unsupported precision or grid).
+ *   sf_corr_direct_lookup: coords / channel order l*81 + a*9 + b' / sampling rule / NaN, infinite and far coordinates exactly as
+ *       sf_corr_lookup (a scaled coordinate not strictly inside (-1e6, 1e6) samples zero; exactly zero where all four taps lie
+ *       outside; -0.0 is 0).  out: fp32 planes [324][h*w] per image (stride out_img_stride floats); out_koct: fp16 k-octet planes
+ *       [41][h*w][8] per image (rows 324..327 zero), bitwise fp16(out) of the same launch.  At least one of the two.
+ *       A workgroup takes 16 consecutive source pixels; per level it walks the bounding box of their clipped windows in chunks of
+ *       16 cells on v_mfma_f32_16x16x32_f16 (chunks no pixel needs are skipped): with smooth flow about twice the needed products,
+ *       with arbitrary coordinates up to pixels x level cells.  Enqueues on `stream` only: no allocation, no synchronisation.
+ *   precision: SF_PRECISION_F16 (one product, fp32 accumulation: the class of the blocked fp16 volume) or SF_PRECISION_F16X3 (three
+ *       products: the class of the blocked fp32 volume); anything else SF_ERR_UNSUPPORTED, as is D > 256.  Cells are never rounded
+ *       to fp16 and never stored, so the values are NOT bitwise the volume routes'; both are held to float64.
+ *   SF_ERR_BAD_ARG: null pointers (both outputs NULL included), a grid below 8 x 8, ws not 16-byte aligned or ws_bytes too small,
+ *       out_koct not 16-byte aligned or its stride no multiple of 8 halves.  f1, f2, coords and out need 4-byte alignment, every
+ *       stride is free.
+ * Established by tests/test_gpu_corr_direct.py (grids 8 x 8 .. 24 x 40, D = 1 .. 256, B x pairs up to 2 x 2 and 1 x 3, noisy, uniform
+ * random, all-dead and opposite-corner coordinates): every channel within the derived bound of tests/corr_direct_cases.py of float64;
+ * the summation order of a cell is fixed (k-steps of 32 ascending; hi*hi, hi*lo, lo*hi per step), so a pixel's 324 values depend on
+ * its own features and coordinates only: unchanged bitwise when its neighbours' coordinates change, image (b, t) of a batch bitwise
+ * the call on that pair alone, placed runs bitwise the contiguous one, out alone / out_koct alone / both bitwise the same. */
+int64_t sf_corr_direct_ws_bytes(int B, int pairs, int D, int h, int w, int precision);
+int sf_corr_direct_pack(const float* f1, const float* f2, int64_t f_clip_stride, int64_t f_pair_stride,
+                        void* ws, int64_t ws_bytes, int B, int pairs, int D, int h, int w, int precision, void* stream);
+int sf_corr_direct_lookup(const void* ws, const float* coords, float* out, int64_t out_img_stride,
+                          void* out_koct, int64_t out_koct_img_stride, int B, int pairs, int D, int h, int w,
+                          int precision, void* stream);
 
 /* ---- generic fused GEMM: every 1x1 conv / nn.Linear / einsum on the path ------------------------
  * C[z][m][n] = epilogue( alpha * ( sum_k A[z][m][k] * B[z][k][n] + bias[m] ) )

@@ -148,6 +148,9 @@ SIGNATURES = {
     "sf_corr_build_blocked32_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "sf_corr_build_blocked32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "sf_corr_lookup_blocked32": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sf_corr_direct_ws_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
+    "sf_corr_direct_pack": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
+    "sf_corr_direct_lookup": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "sf_gemm": (_i, [C.POINTER(SfGemm), _vp]),
     "sf_gemm_route": (_i, [C.POINTER(SfGemm), C.POINTER(SfGemmRoute)]),
     "sf_gemm_split_ws_floats": (_i64, [_i, _i, _i, _i]),
@@ -248,7 +251,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 138:
+    if lib.sf_version() < 139:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

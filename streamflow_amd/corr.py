@@ -19,6 +19,9 @@ class CorrBlock:
     cells built with single f16 MFMA products -- the bf16/fp16 volume configurations of BASELINE.json.
     ``layout="blocked"`` keeps them in cache-line blocks -- 8 x 8 fp16 cells (csrc/corr_blocked.hip) or 4 rows x 8 columns of
     fp32 cells (csrc/corr_blocked32.hip) -- what the fused engine uses; ``corr_pyramid`` is then a row-major COPY made on first access.
+    ``layout="direct"`` keeps NO volume: the features are packed once (csrc/corr_direct.hip) and every call computes the cells its
+    windows touch; ``dtype`` selects the class (float16: one fp16 product, float32: three split products).  ``corr_pyramid`` is then
+    computed on first access by ``CorrBlock.corr`` and pooling (reference shapes, a copy).
     """
 
     @ops.on_tensor_device
@@ -37,10 +40,17 @@ class CorrBlock:
         N = h * w
         if dtype not in (torch.float32, torch.float16):
             raise RuntimeError(f"CorrBlock: volume dtype must be float32 or float16, got {dtype}")
-        if layout not in ("rows", "blocked"):
-            raise RuntimeError("CorrBlock: layout must be 'rows' or 'blocked'")
+        if layout not in ("rows", "blocked", "direct"):
+            raise RuntimeError("CorrBlock: layout must be 'rows', 'blocked' or 'direct'")
         self._keep = (f1, f2)
-        self.vol = None
+        self.vol = self.direct_ws = None
+        if layout == "direct":
+            self.D = D
+            self.direct_prec = ops.PRECISION_F16 if dtype == torch.float16 else ops.PRECISION_F16X3
+            self.direct_ws = torch.empty(ops.corr_direct_ws_bytes(B, 1, D, h, w, self.direct_prec), dtype=torch.uint8, device=f1.device)
+            ops.corr_direct_pack(f1.data_ptr(), f2.data_ptr(), D * N, 0, self.direct_ws, B, 1, D, h, w, self.direct_prec)
+            self._pyr = self._store = self.pitch = None
+            return
         if layout == "blocked":
             self.vol = ops.new_blocked_volume(B, h, w, f1.device, f32=dtype == torch.float32)
             ops.corr_build_blocked(f1.data_ptr(), f2.data_ptr(), D * N, 0, self.vol, B, 1, D)
@@ -57,6 +67,12 @@ class CorrBlock:
 
     @property
     def corr_pyramid(self):
+        if self._pyr is None and self.direct_ws is not None:   # no volume is kept: the reference's own construction, on first access
+            B, h, w = self.shape
+            c = CorrBlock.corr(*self._keep).reshape(B * h * w, 1, h, w)
+            self._pyr = [c]
+            for _ in range(3):
+                self._pyr.append(torch.nn.functional.avg_pool2d(self._pyr[-1], 2, stride=2))
         if self._pyr is None:                                  # blocked volumes: row-major copy, reference shapes
             B, h, w = self.shape
             self._pyr = [t.reshape(B * h * w, 1, h >> l, w >> l) for l, t in enumerate(self.vol.levels())]
@@ -69,7 +85,9 @@ class CorrBlock:
         ops._dev_check(c)
         assert tuple(c.shape) == (B, 2, h, w), (c.shape, self.shape)
         out = torch.empty(B, 4 * 81, h, w, dtype=torch.float32, device=c.device)
-        if self.vol is not None:
+        if self.direct_ws is not None:
+            ops.corr_direct_lookup(self.direct_ws, Planes.of(c), Planes.of(out), None, B, 1, self.D, h, w, self.direct_prec)
+        elif self.vol is not None:
             ops.corr_lookup_blocked(self.vol, Planes.of(c), Planes.of(out), None, B, 1)
         else:
             ops.corr_lookup(self._store, None, Planes.of(c), Planes.of(out), B, 1, h, w, pitch=self.pitch)

@@ -162,7 +162,7 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                   png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90,
                                   jpeg_split: str = "auto", bidirectional: bool = False, occlusion_dir: str = None,
                                   warp_dir: str = None, report: bool = False, interpolate: int = None, slowmo_dir: str = None,
-                                  slowmo_video: str = None) -> int:
+                                  slowmo_video: str = None, corr: str = None) -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
     baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
@@ -183,7 +183,9 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     interpolate: an integer factor 2 .. 64: the video with `interpolate` times as many frames (streamflow_amd.interpolate: forward
     splatting along both flows, interpolate - 1 frames between every two; implies bidirectional), written as
     ``slowmo_dir/slow_%06d.png`` (where `png_encode` says) and / or as one Motion-JPEG AVI file `slowmo_video` (`fps`,
-    `jpeg_quality`); the input frames are passed through.  With `report` one more line gives the shares of the cover codes."""
+    `jpeg_quality`); the input frames are passed through.  With `report` one more line gives the shares of the cover codes.
+
+    corr: None / "volume" = the all-pairs correlation volume, "direct" = on-demand correlation from features (StreamFlowT4(corr=...))."""
     import os
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
@@ -192,7 +194,7 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     if not torch.cuda.is_available():
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
-    model = StreamFlowT4(ckpt).to(device).eval()
+    model = StreamFlowT4(ckpt, corr=corr).to(device).eval()
     if (interpolate is None) != (not slowmo_dir and not slowmo_video):
         raise ValueError("read_frames_and_group_predict: `interpolate` and a slow-motion output (slowmo_dir, slowmo_video) come together")
     bidirectional = bool(bidirectional or occlusion_dir or warp_dir or report or interpolate)
@@ -347,6 +349,8 @@ def arg_parser():
     ap.add_argument("--slowmo", default=None, metavar="DIR", help="directory for the frames of the slow-motion video, slow_%%06d.png")
     ap.add_argument("--slowmo-video", default=None, metavar="FILE.avi",
                     help="the slow-motion video as one Motion-JPEG AVI file (--fps, --jpeg-quality), encoded on the GPU")
+    ap.add_argument("--corr", default=None, choices=("volume", "direct"),
+                    help="correlation route: the all-pairs volume (default) or on-demand lookups from features (no N x N buffer)")
     return ap
 
 
@@ -362,7 +366,7 @@ def main(argv=None) -> int:
                                       save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode,
                                       png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality, jpeg_split=a.jpeg_split,
                                       bidirectional=a.bidirectional, occlusion_dir=a.occlusion, warp_dir=a.warp, report=a.report,
-                                      interpolate=a.interpolate, slowmo_dir=a.slowmo, slowmo_video=a.slowmo_video)
+                                      interpolate=a.interpolate, slowmo_dir=a.slowmo, slowmo_video=a.slowmo_video, corr=a.corr)
     print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp, a.slowmo, a.slowmo_video) if d))
     return 0
 

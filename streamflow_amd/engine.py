@@ -72,6 +72,10 @@ class EngineOptions:
     stored_auto_max_gb: int = 16     # ... when the weight buffer stays under this size
     stored_p_max_gb: int = 64        # gma_mode 'stored': largest weight buffer (n_img * Ppad^2 * 2 bytes) kept; beyond it the fused recompute runs
     max_plans: int = 4               # buffer sets (and graphs) kept, least recently used evicted
+    corr_direct: bool = False        # no N x N volume: the correlation features are computed at every lookup from packed features
+                                     # (csrc/corr_direct.hip; 1.33 N D halves per frame instead of 1.33 N^2 cells per pair).  Not bitwise the
+                                     # volume route's results (cells are never rounded or stored); not with precision='fp32'
+    corr_direct_min_px: int = 0      # grids of at least this many pixels take that route; 0: never (measurements: DESIGN.md section 5.11)
 
     @staticmethod
     def from_env(base: Optional["EngineOptions"] = None) -> "EngineOptions":
@@ -370,11 +374,25 @@ def resolve_gma(gma_mode: str, precision: int, flash_qk_products: int, options: 
     return GmaPlan(form, 1, False, ks, n_store, project_v, bool(auto_stored and n_store > 0))
 
 
+def resolve_corr(options: EngineOptions, precision: int, corr_f16: bool, P: int) -> str:
+    """'direct' (correlation features computed at every lookup from packed features, csrc/corr_direct.hip) or 'volume' (the all-pairs
+    pyramid built once per clip) for a grid of P pixels; the only place that decides.  The direct route runs in the class of the volume
+    it replaces: one fp16 product for fp16 volumes (corr_f16), three split products for fp32 volumes -- there is no exact-fp32 form, so
+    precision='fp32' refuses it as it refuses the fused GMA modes."""
+    del corr_f16                                   # (both volume formats have a direct class)
+    direct = bool(options.corr_direct) or (int(options.corr_direct_min_px) > 0 and P >= int(options.corr_direct_min_px))
+    if direct and precision == ops.PRECISION_FP32:
+        raise RuntimeError("corr_direct needs a split precision (f16x3 / f16x2 / f16): the on-demand correlation has no exact fp32 "
+                           "form; precision='fp32' keeps the volume")
+    return "direct" if direct else "volume"
+
+
 class _Plan:
     """Buffers for one (clips, pairs, h, w) shape; of the GMA buffers only those that the form `gma` reads."""
 
     def __init__(self, W: HotPathWeights, Bc: int, h: int, w: int, D: int, device, gma: GmaPlan, corr_f16: bool = False,
-                 shadows: bool = False, corr_blocked: bool = False, koct_io: bool = False, corr_blocked32: bool = False):
+                 shadows: bool = False, corr_blocked: bool = False, koct_io: bool = False, corr_blocked32: bool = False,
+                 corr_direct: bool = False):
         Pn = W.pairs
         n, P = Bc * Pn, h * w
         self.Bc, self.Pn, self.h, self.w, self.n, self.P, self.D = Bc, Pn, h, w, n, P, D
@@ -394,7 +412,15 @@ class _Plan:
         self.corr_blocked = bool(corr_blocked and corr_f16 and shadows)
         # blocked fp32 volumes (csrc/corr_blocked32.hip): same idea with 4-row x 8-column blocks; the features leave as fp32 planes
         self.corr_blocked32 = bool(corr_blocked32 and not corr_f16)
-        if self.corr_blocked32:
+        # no volume at all (csrc/corr_direct.hip): the packed features of every pair; the features leave in the formats of the volume
+        # route they replace (k-octets only under corr_blocked's conditions, fp32 planes otherwise)
+        self.corr_direct = bool(corr_direct)
+        self.corr_prec = ops.PRECISION_F16 if corr_f16 else ops.PRECISION_F16X3
+        if self.corr_direct:
+            self.vol = self.lvls = None
+            self.corr_pitch = None
+            self.corr_ws = torch.empty(ops.corr_direct_ws_bytes(Bc, Pn, D, h, w, self.corr_prec), dtype=torch.uint8, device=device)
+        elif self.corr_blocked32:
             self.vol = ops.new_blocked_volume(n, h, w, device, f32=True)
             self.lvls = None
             self.corr_pitch = None
@@ -476,6 +502,8 @@ class _Plan:
         """Level l of the row-major volumes as [pairs, clips * N, h_l, w_l] -- per pair the reference's corr_pyramid[l] (corr.py:13-21)
         without its singleton dimension -- a strided VIEW of the (possibly row-pitched, _Plan.corr_pitch) storage; a copy for blocked volumes."""
         hl, wl = self.h >> l, self.w >> l
+        if self.corr_direct:
+            raise RuntimeError("this plan keeps no correlation volume (corr_direct): there is no 'volume' to tap")
         if self.lvls is None:                      # blocked volumes (image = clip * pairs + pair): a row-major COPY, tests only
             t = self.vol.levels()[l].view(self.Bc, self.Pn, self.P, hl, wl)
             return t.permute(1, 0, 2, 3, 4).reshape(self.Pn, self.Bc * self.P, hl, wl)
@@ -602,11 +630,12 @@ class HotPathEngine:
                           project_ok=shadows and self.W.to_v.M == self.W.to_v.K == HDIM and self.W.to_v.bias is None)
         pl = self._plans.pop(key, None)
         blocked32 = bool(self.corr_blocked32 and self.precision != ops.PRECISION_FP32)     # (exact fp32: never the split-fp16 blocked build)
-        if pl is None or pl.gma != gma or pl.corr_blocked32 != blocked32:   # (a mode or precision assigned after the plan was made)
+        direct = resolve_corr(self.options, self.precision, self.corr_f16, h * w) == "direct"
+        if pl is None or pl.gma != gma or pl.corr_blocked32 != blocked32 or pl.corr_direct != direct:   # (a mode or precision assigned after the plan was made)
             while len(self._plans) >= max(1, self.max_plans):
                 self._plans.pop(next(iter(self._plans)))            # dicts keep insertion order: first = oldest
             pl = _Plan(self.W, Bc, h, w, D, self.device, gma, corr_f16=self.corr_f16, shadows=shadows,
-                       corr_blocked=self.corr_blocked, corr_blocked32=blocked32,
+                       corr_blocked=self.corr_blocked, corr_blocked32=blocked32, corr_direct=direct,
                        koct_io=self.options.koct_io and self.options.hidden_koct)   # (k-octet-only blocks need k-octet producers)
         self._plans[key] = pl                                        # (re)insert as most recent
         return pl
@@ -729,7 +758,10 @@ class HotPathEngine:
             elif pl.gma.form == "matrix":
                 self._attention_rows(cs, pl, 0, P)
         # a1+a2: all pairs, one launch.  pair t = (frame t, frame t+1)
-        if pl.corr_blocked or pl.corr_blocked32:
+        if pl.corr_direct:                          # no volume: f1 and the pooled pyramid of f2 in the operand format, once per clip
+            ops.corr_direct_pack(fmaps.data_ptr(), fmaps.data_ptr() + 4 * D * P, T * D * P, D * P, pl.corr_ws, Bc, Pn, D, h, w,
+                                 pl.corr_prec)
+        elif pl.corr_blocked or pl.corr_blocked32:
             ops.corr_build_blocked(fmaps.data_ptr(), fmaps.data_ptr() + 4 * D * P, T * D * P, D * P, pl.vol, Bc, Pn, D,
                                    ws=pl.corr_ws)
         else:
@@ -765,7 +797,12 @@ class HotPathEngine:
             ops.gemm(W.convf1, pl.flow, pl.f128, EPI_NONE, cx=cs)
             run_skblock(W.convf2, pl.f128, pl.cat256.slice(192, 256), pl.hid2, pl.xa2, pl.xb2, h, w, cx=cs)
         # ... while the main stream does a3 (correlation lookup for all pairs, streamflow.py:132) and the corr branch
-        if pl.corr_blocked:
+        if pl.corr_direct and pl.corr_blocked:
+            ops.corr_direct_lookup(pl.corr_ws, pl.coords1, None, pl.corr, Bc, Pn, pl.D, h, w, pl.corr_prec)
+        elif pl.corr_direct:
+            ops.corr_direct_lookup(pl.corr_ws, pl.coords1, replace(pl.corr, shadow=None), None, Bc, Pn, pl.D, h, w, pl.corr_prec)
+            ops.refresh_shadow(pl.corr, cx)
+        elif pl.corr_blocked:
             ops.corr_lookup_blocked(pl.vol, pl.coords1, None, pl.corr, Bc, Pn)
         elif pl.corr_blocked32:
             ops.corr_lookup_blocked(pl.vol, pl.coords1, replace(pl.corr, shadow=None), None, Bc, Pn)

@@ -476,7 +476,8 @@ def validate_kitti_tile(model: Callable, iters: int = 6, root: Optional[str] = N
 
 
 # ---- command line (the reference's evaluate_mf.py --dataset switch) -----------------------------------------------------------
-def load_model(ckpt: str, T: int = 4, preset: Optional[str] = None, device: Optional[torch.device] = None):
+def load_model(ckpt: str, T: int = 4, preset: Optional[str] = None, device: Optional[torch.device] = None,
+               corr: Optional[str] = None):
     """SKFlow_MF8 for clips of T frames with the checkpoint loaded strictly, as StreamFlowT4 loads it ({'model': state_dict} or a
     bare dict, keys optionally prefixed 'module.'), on `device` (default: the current GPU) in eval mode."""
     from .model import SKFlow_MF8, default_args
@@ -487,7 +488,7 @@ def load_model(ckpt: str, T: int = 4, preset: Optional[str] = None, device: Opti
     obj = torch.load(ckpt, map_location="cpu")
     sd = obj["model"] if isinstance(obj, dict) and "model" in obj else obj
     sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
-    model = SKFlow_MF8(default_args(T=T, preset=preset))
+    model = SKFlow_MF8(default_args(T=T, preset=preset, corr=corr))
     model.load_state_dict(sd, strict=True)
     for p in model.parameters():
         p.requires_grad = False
@@ -510,9 +511,11 @@ def main(argv=None) -> int:
     ap.add_argument("--flo5-decode", default="gpu", choices=("gpu", "host"),
                     help="where Spring's .flo5 ground truth is inflated and put together (--dataset spring; the same bits either way)")
     ap.add_argument("--preset", default=None, help="arithmetic preset (streamflow_amd.presets); default: fp32_class")
+    ap.add_argument("--corr", default=None, choices=("volume", "direct"),
+                    help="correlation route: the all-pairs volume (default) or on-demand lookups from features (no N x N buffer)")
     a = ap.parse_args(argv)
     png_decode = a.png_decode if a.clips_per_step > 1 else "host"
-    model = load_model(a.ckpt, T=a.T, preset=a.preset)
+    model = load_model(a.ckpt, T=a.T, preset=a.preset, corr=a.corr)
     if a.dataset == "sintel":
         res = validate_sintel_mf(model, iters=a.iters, root=a.root, nframes=a.T, clips_per_step=a.clips_per_step, png_decode=png_decode)
     elif a.dataset == "sintel_occ":

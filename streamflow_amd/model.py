@@ -25,12 +25,13 @@ from .update import SKUpdateBlock_TAM_v3
 UPDATE_BLOCKS = {"SKUpdateBlock_TAM_v3": SKUpdateBlock_TAM_v3}
 
 
-def default_args(T: int = 4, Encoder: str = "Twins_CSC", **kw) -> Namespace:
-    """The canonical StreamFlow flag set (reference scripts/infer.sh:12-26, train_mf.py:375,396,462)."""
+def default_args(T: int = 4, Encoder: str = "Twins_CSC", corr: Optional[str] = None, **kw) -> Namespace:
+    """The canonical StreamFlow flag set (reference scripts/infer.sh:12-26, train_mf.py:375,396,462).  corr: None / "volume" = the
+    all-pairs correlation volume, "direct" = on-demand correlation from features (EngineOptions.corr_direct)."""
     a = Namespace(model_name="SKFlow_MF8", Encoder=Encoder, UpdateBlock="SKUpdateBlock_TAM_v3",
                   MotionEncoder="SKMotionEncoder6_Deep_nopool_res", use_gma=True, k_conv=[1, 15],
                   PCUpdater_conv=[1, 7], T=T, num_heads=1, decoder_dim=256, mixed_precision=False, dropout=0,
-                  corr_levels=4, corr_radius=4, use_graph=False, preset=None)
+                  corr_levels=4, corr_radius=4, use_graph=False, preset=None, corr=corr)
     for k, v in kw.items():
         setattr(a, k, v)
     return a
@@ -79,14 +80,24 @@ class SKFlow_MF8(nn.Module):
             raise RuntimeError(f"unknown preset {name!r} (have {list(presets.PRESETS)})")
         return name
 
+    def corr_route(self) -> Optional[str]:
+        """`args.corr`: None (the engine's options decide: the volume unless SF_ENGINE_OPTS says otherwise), "volume" or "direct"."""
+        corr = getattr(self.args, "corr", None)
+        if corr not in (None, "volume", "direct"):
+            raise RuntimeError(f"args.corr must be None, 'volume' or 'direct', got {corr!r}")
+        return corr
+
     def engine(self, device) -> HotPathEngine:
         from . import presets
+        from .engine import EngineOptions
+        corr = self.corr_route()
         params = [p for n, p in self.named_parameters() if n.startswith(("att.", "update_block."))]
         name = self.preset_name()
-        key = (str(device), name) + tuple((p.data_ptr(), p._version) for p in params)
+        key = (str(device), name, corr) + tuple((p.data_ptr(), p._version) for p in params)
         if self._engine is None or self._engine_key != key:
             self._engine = HotPathEngine(self._hot_state(), device=device, T=self.args.T,
                                          use_graph=bool(getattr(self.args, "use_graph", False)),
+                                         options=None if corr is None else EngineOptions(corr_direct=corr == "direct"),
                                          **presets.engine_kwargs(name))
             self._engine_key = key
         return self._engine
@@ -181,9 +192,10 @@ class StreamFlowT4(SKFlow_MF8):
     bare dict, keys optionally prefixed 'module.').  With the default Twins_CSC encoder the whole checkpoint is loaded
     strictly (demo.py:388-389); with a stand-in encoder only the hot-path keys are (and must match exactly)."""
 
-    def __init__(self, ckpt=None, Encoder: str = "Twins_CSC", use_graph: bool = True, preset: Optional[str] = None):
+    def __init__(self, ckpt=None, Encoder: str = "Twins_CSC", use_graph: bool = True, preset: Optional[str] = None,
+                 corr: Optional[str] = None):
         # the reference's demo hard-wires autocast(enabled=True) (demo.py:427,439,456): reduced-precision class by default
-        super().__init__(default_args(T=4, Encoder=Encoder, use_graph=use_graph, mixed_precision=True, preset=preset))
+        super().__init__(default_args(T=4, Encoder=Encoder, use_graph=use_graph, mixed_precision=True, preset=preset, corr=corr))
         if ckpt is not None:
             obj = torch.load(ckpt, map_location="cpu") if isinstance(ckpt, (str, bytes)) or hasattr(ckpt, "read") else ckpt
             sd = obj["model"] if isinstance(obj, dict) and "model" in obj else obj

@@ -2053,6 +2053,43 @@ def corr_lookup_blocked(vol: BlockedVolume, coords: Planes, out: Optional[Planes
         0 if out_koct is None else out_koct.img_stride, B, pairs, h, w, _lib.stream()), "sf_corr_lookup_blocked"))
 
 
+def corr_direct_ws_bytes(B: int, pairs: int, D: int, h: int, w: int, precision: int = PRECISION_F16) -> int:
+    """Bytes of the packed features of the volume-free route (csrc/corr_direct.hip): f1 and the four-level pyramid of f2."""
+    return int(_lib.load().sf_corr_direct_ws_bytes(B, pairs, D, h, w, precision))
+
+
+@on_tensor_device
+def corr_direct_pack(f1_ptr: int, f2_ptr: int, clip_stride: int, pair_stride: int, ws: torch.Tensor, B: int, pairs: int,
+                     D: int, h: int, w: int, precision: int = PRECISION_F16) -> None:
+    """Once per clip: f1 and the pooled pyramid of f2 into `ws` (uint8, corr_direct_ws_bytes() bytes, 16-byte aligned)."""
+    N = h * w
+    need = corr_direct_ws_bytes(B, pairs, D, h, w, precision)
+    assert ws.dtype == torch.uint8 and ws.numel() >= need
+    nbytes = B * pairs * (2.0 * N * D * 4 + need / (B * pairs))       # both feature maps read once + the workspace written once
+    _launch("corr_direct_pack", 0, nbytes, lambda: _lib.check(_lib.load().sf_corr_direct_pack(
+        f1_ptr, f2_ptr, clip_stride, pair_stride, ws.data_ptr(), need, B, pairs, D, h, w, precision, _lib.stream()),
+        "sf_corr_direct_pack"))
+
+
+@on_tensor_device
+def corr_direct_lookup(ws: torch.Tensor, coords: Planes, out: Optional[Planes], out_koct: Optional[Planes], B: int, pairs: int,
+                       D: int, h: int, w: int, precision: int = PRECISION_F16) -> None:
+    """a3 from the packed features: `out_koct` (fp16 k-octet planes of the 324 features) and / or `out` (fp32 planes)."""
+    N = h * w
+    assert coords.img_stride == 2 * N
+    assert out is None or (out.rows == 324 and out.n_img == B * pairs and not out.f16)
+    assert out_koct is None or (out_koct.rows == 324 and out_koct.n_img == B * pairs and out_koct.koct)
+    parts = 2 if precision == PRECISION_F16X3 else 1
+    cells = sum((h >> l) * (w >> l) for l in range(4))
+    # algorithmic bytes per image: the packed features read once + coords + the outputs written
+    nbytes = B * pairs * ((N + cells) * D * 2.0 * parts + N * 2 * 4.0 + N * 324 * 4.0 * (out is not None)
+                          + N * 328 * 2.0 * (out_koct is not None))
+    _launch("corr_lookup", 2.0 * 400 * D * N * B * pairs, nbytes, lambda: _lib.check(_lib.load().sf_corr_direct_lookup(
+        ws.data_ptr(), coords.ptr, None if out is None else out.ptr, 0 if out is None else out.img_stride,
+        None if out_koct is None else out_koct.ptr, 0 if out_koct is None else out_koct.img_stride, B, pairs, D, h, w,
+        precision, _lib.stream()), "sf_corr_direct_lookup"), products=_products(precision))
+
+
 @on_tensor_device
 def bilinear_sampler(img: torch.Tensor, coords: torch.Tensor, want_mask: bool = False):
     _dev_check(img)
