@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 139
+#define SF_VERSION 140
 
 enum {
     SF_OK = 0,
@@ -1015,6 +1015,56 @@ int sf_frame_interp_phases(const uint8_t* a, int64_t a_frame_stride, int64_t a_r
                            int w, int num, int den, const uint8_t* cls_f, const uint8_t* cls_b, uint8_t code_visible,
                            uint8_t code_occluded, int imp_vis, int imp_occ, int imp_other, uint8_t* out, uint8_t* cover, double* stats,
                            void* ws, int64_t ws_bytes, int phases, void* stream);
+
+/* ---- resize: separable resampling of uint8 frames and fp32 flow planes with caller-built tables (csrc/resize.hip) -----------------
+ * Running the model at a chosen resolution: frames are resampled to the working size, the flows back to the frames' own grid.  The
+ * coefficient tables are built by the caller on the host (streamflow_amd.resize.coeff_table: a few hundred doubles per axis, the
+ * filters' sin / polynomial evaluated in float64 once per (in, out, filter)) and passed as DEVICE pointers; the kernels do the
+ * per-pixel arithmetic only.  Per axis, for an output of `out` positions from an input of `in`:
+ *     bounds int32 [out][2]:  (first tap, tap count), 0 <= first, first + count <= in, count <= ksize,
+ *     k      [out][ksize]:    the coefficient of tap first + i at [o][i]; entries past the count are not read.
+ *
+ * sf_resize_u8: n frames uint8 with 3 channels, byte (i, y, x, ch) at src + i frame_stride + y row_stride + x px_stride +
+ *   ch ch_stride (bytes, >= 0, as sf_warp_frames' src: HWC, CHW and views need no copy), from H x W to h x w; out uint8
+ *   [n][h][w][3] dense (the layout sf_frames_to_clips' fast path reads).  k is int32, the coefficients scaled by 2^22.  This is
+ *   Pillow's ImagingResample for 8-bit images:
+ *     a horizontal pass runs only if w != W:  t[i][y][x][ch] = clip8(2^21 + sum_j src[i][y][first_x(x) + j][ch] * kx[x][j]),  y < H,
+ *     then a vertical pass only if h != H:    out[i][y][x][ch] = clip8(2^21 + sum_j t[i][first_y(y) + j][x][ch] * ky[y][j]),
+ *     clip8(ss) = clamp(ss >> 22, 0, 255) (arithmetic shift); the sums are 32-bit integers; the intermediate t is uint8
+ *     [n][H][w][3] in `ws`; with one pass its result goes straight to out, with none the call is a copy into the dense layout.
+ *   ws: sf_resize_u8_ws_bytes(n, H, W, h, w) = 3 n H w bytes when both passes run, else 0 (ws may then be NULL); 4-byte aligned.
+ *   Tables of an axis that has no pass are not read and may be NULL.
+ * sf_resize_f32: n fields of two fp32 planes, u of field i at src + i field_stride + y row_stride + x, v at the same + ch_stride
+ *   (floats, as sf_flow_consistency's fwd), from H x W to h x w; out fp32 [n][2][h][w] dense.  k is fp32 (the float64 table rounded
+ *   once).  The same two passes in fp32, every product and every sum rounded on its own, in tap order from acc = 0:
+ *     acc = acc + v[first + j] * k[o][j],  j = 0 .. count - 1;   the intermediate is fp32 [n][2][H][w] in `ws`;
+ *   on the final store (of whichever pass is last, or of the copy) channel 0 is multiplied by sx and channel 1 by sy (flows resized
+ *   to another grid are in that grid's pixels: sx = w / W, sy = h / H; 1 for plain resampling).  Every tap inside a position's
+ *   bounds is multiplied, zero coefficients included: where the output is NaN is a function of the table and of where the input is
+ *   not finite, nothing else.  ws: sf_resize_f32_ws_bytes(n, H, W, h, w) = 8 n H w bytes when both passes run, else 0.
+ *
+ * Addressing: no address depends on pixel data.  The only data-dependent indices are the tables' first + j: each is clamped into
+ * [0, in - 1] in the kernel and the count into [0, ksize], so no table content can form an address outside the image; a wrong table
+ * gives wrong pixels and nothing else.
+ * Launches: one per pass (memory-bound work), one copy launch when neither axis changes.  Horizontal: a block owns 64 output
+ * columns for 16 rows and stages its 64 table rows in LDS; a thread owns one output pixel.  Vertical: a block owns (part of) one
+ * output row, its coefficients are wave-uniform; u8: a thread owns four consecutive bytes of the packed 3 w-byte row, with dword
+ * loads and stores where the source is packed (px_stride 3, ch_stride 1), 3 w % 4 == 0 and src, its row / frame strides, are
+ * 4-byte aligned, byte accesses otherwise.  Enqueued on `stream`, no host synchronisation, nothing allocated.
+ * SF_ERR_BAD_ARG before any launch for: a null src or out, a null table of an axis that has a pass, a null ws where one is needed;
+ * H, W, h, w <= 0; H W, h w or H w >= 2^30; n outside 1 .. 65535 (u8) / 1 .. 32767 (f32); ksize of an axis that has a pass outside
+ * 1 .. SF_RESIZE_MAX_KSIZE (97: a 16-fold reduction with the 3-lobe filter, 2 * 48 + 1 taps); negative byte strides (u8), a row
+ * stride < W, a zero channel stride, a negative field stride (f32); out, ws or a table not 4-byte aligned (f32: src too); ws_bytes
+ * too small.  The *_ws_bytes functions return SF_ERR_BAD_ARG for n, H, W, h, w outside the limits. */
+#define SF_RESIZE_MAX_KSIZE 97
+int64_t sf_resize_u8_ws_bytes(int n, int H, int W, int h, int w);
+int sf_resize_u8(const uint8_t* src, int64_t frame_stride, int64_t row_stride, int64_t px_stride, int64_t ch_stride, int n, int H, int W,
+                 int h, int w, const int32_t* bounds_x, const int32_t* kx, int ksize_x, const int32_t* bounds_y, const int32_t* ky,
+                 int ksize_y, uint8_t* out, void* ws, int64_t ws_bytes, void* stream);
+int64_t sf_resize_f32_ws_bytes(int n, int H, int W, int h, int w);
+int sf_resize_f32(const float* src, int64_t field_stride, int64_t ch_stride, int64_t row_stride, int n, int H, int W, int h, int w,
+                  const int32_t* bounds_x, const float* kx, int ksize_x, const int32_t* bounds_y, const float* ky, int ksize_y, float sx,
+                  float sy, float* out, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- PNG frames: row unfiltering of inflated IDAT streams (PNG specification, section 9; flow_io.read_png on the host) ----------
  * The host inflates (zlib); the device undoes the row filters of a whole batch of equally shaped images in one launch, so the

@@ -207,6 +207,10 @@ SIGNATURES = {
                              _i, _i, _vp, _vp, C.c_uint8, C.c_uint8, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sf_frame_interp_phases": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i,
                                     _i, _i, _i, _i, _vp, _vp, C.c_uint8, C.c_uint8, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "sf_resize_u8_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "sf_resize_u8": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "sf_resize_f32_ws_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "sf_resize_f32": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp]),
     "sf_frames_to_clips": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_clips_to_flows": (_i, [C.POINTER(SfPairPtrs), _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sf_png_unfilter": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i64, _i, _vp]),
@@ -251,7 +255,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 139:
+    if lib.sf_version() < 140:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

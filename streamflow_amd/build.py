@@ -22,7 +22,7 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libstreamflow_hip.so")
 ASAN_OBJ = os.path.join(CSRC, "build_asan")
 ASAN_LIB = os.path.join(HERE, "libstreamflow_hip_asan.so")
-SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "corr_direct.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip", "flow_score_batch.hip", "flow_consistency.hip", "frame_interp.hip", "video_io.hip", "png_unfilter.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "flo5_encode.hip", "flo5_decode.hip"]
+SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "corr_direct.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip", "flow_score_batch.hip", "flow_consistency.hip", "frame_interp.hip", "resize.hip", "video_io.hip", "png_unfilter.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "flo5_encode.hip", "flo5_decode.hip"]
 HEADERS = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "weight_ring.h"), os.path.join(CSRC, "gemm_epilogue.h"),
            os.path.join(CSRC, "split_operand.h"), os.path.join(CSRC, "huff_deflate.h"), os.path.join(CSRC, "inflate_core.h"), os.path.join(CSRC, "jpeg_decode_core.h"), os.path.join(CSRC, "jpeg_sync_core.h"), os.path.join(HERE, "..", "include", "streamflow_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall",
@@ -34,7 +34,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # step's kernel table (profiles/r*_kernel_stats_sintel_serial.md)
 HOT_KERNELS = ("gemm_bstat", "ffn_pair_kernel", "sk_tail_kernel", "gma_flash_pipe_kernel", "gma_pv_kernel", "temporal_block_kernel", "mask_upsample_kernel", "gemm_bdirect_kernel", "gma_flash_kernel", "flash_project_v_kernel", "dwconv_mfma_kernel",
                "corr_lookup_blocked_kernel", "corr_build_blocked_kernel", "corr_lookup_blocked32_kernel", "corr_build_blocked32_kernel", "corr_direct_lookup_kernel", "corr_direct_pack_kernel", "temporal_attn_kernel", "layernorm_cm_split_kernel",
-               "flash_pack_v_kernel", "flow_score_kernel", "flow_score_batch_kernel", "flow_consistency_kernel", "warp_frames_kernel", "splat_kernel", "resolve_kernel", "interp_finish_kernel", "frames_to_clips_kernel", "clips_to_flows_kernel", "png_unfilter_kernel",
+               "flash_pack_v_kernel", "flow_score_kernel", "flow_score_batch_kernel", "flow_consistency_kernel", "warp_frames_kernel", "splat_kernel", "resolve_kernel", "interp_finish_kernel", "resize_h_u8_kernel", "resize_v_u8_kernel", "resize_copy_u8_kernel", "resize_h_f32_kernel", "resize_v_f32_kernel", "resize_copy_f32_kernel", "frames_to_clips_kernel", "clips_to_flows_kernel", "png_unfilter_kernel",
                "png_filter_kernel", "png_table_kernel", "png_offsets_kernel", "png_pack_kernel", "flow_to_kitti16_kernel",
                "flo5_shuffle_kernel", "flo5_table_kernel", "flo5_offsets_kernel", "flo5_pack_kernel",
                "inflate_kernel", "flo5_assemble_kernel",

@@ -162,7 +162,8 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                   png_encode: str = "host", video_path: str = None, fps: float = 8, jpeg_quality: int = 90,
                                   jpeg_split: str = "auto", bidirectional: bool = False, occlusion_dir: str = None,
                                   warp_dir: str = None, report: bool = False, interpolate: int = None, slowmo_dir: str = None,
-                                  slowmo_video: str = None, corr: str = None) -> int:
+                                  slowmo_video: str = None, corr: str = None, scale: float = None, max_side: int = None,
+                                  resize_filter: str = "bilinear") -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
     baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
@@ -185,12 +186,23 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     ``slowmo_dir/slow_%06d.png`` (where `png_encode` says) and / or as one Motion-JPEG AVI file `slowmo_video` (`fps`,
     `jpeg_quality`); the input frames are passed through.  With `report` one more line gives the shares of the cover codes.
 
-    corr: None / "volume" = the all-pairs correlation volume, "direct" = on-demand correlation from features (StreamFlowT4(corr=...))."""
+    corr: None / "volume" = the all-pairs correlation volume, "direct" = on-demand correlation from features (StreamFlowT4(corr=...)).
+
+    scale / max_side (at most one of them): the model runs at resize.scaled_size(frame size, scale, max_side), the frames resampled
+    on the GPU with `resize_filter` and the flows brought back to the frames' own grid (video.predict_video(..., size=...)); every
+    output keeps the original size.  Neither: the frames go through as they are."""
     import os
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
     _check_png_encode(png_encode)
     frames = video.open_frames(path, png_decode, jpeg_split)
+    resized = {}
+    if scale is not None or max_side is not None:
+        from . import resize
+        if resize_filter not in resize.FILTERS:
+            raise ValueError(f"read_frames_and_group_predict: resize_filter {resize_filter!r} (one of {', '.join(resize.FILTERS)})")
+        resized = dict(size=resize.scaled_size(frames.hw, scale=scale, max_side=max_side), frame_filter=resize_filter,
+                       flow_filter=resize_filter)
     if not torch.cuda.is_available():
         raise RuntimeError("read_frames_and_group_predict runs on the GPU; there is no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -283,9 +295,10 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     try:
         if bidirectional:
             video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device,
-                                sink=sink_both, bidirectional=True)
+                                sink=sink_both, bidirectional=True, **resized)
         else:
-            video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink)
+            video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device, sink=sink,
+                                **resized)
         if slow is not None:
             slow.finish()
     finally:
@@ -351,6 +364,12 @@ def arg_parser():
                     help="the slow-motion video as one Motion-JPEG AVI file (--fps, --jpeg-quality), encoded on the GPU")
     ap.add_argument("--corr", default=None, choices=("volume", "direct"),
                     help="correlation route: the all-pairs volume (default) or on-demand lookups from features (no N x N buffer)")
+    ap.add_argument("--scale", type=float, default=None, metavar="S",
+                    help="run the model at S times the frame size (sides rounded to multiples of 8); the outputs keep the original size")
+    ap.add_argument("--max-side", type=int, default=None, metavar="N",
+                    help="run the model with the longer side at most N pixels (never enlarges); not together with --scale")
+    ap.add_argument("--resize-filter", default="bilinear", choices=("box", "bilinear", "bicubic", "lanczos"),
+                    help="resampling filter of --scale / --max-side, for the frames and for the flows on their way back")
     return ap
 
 
@@ -362,11 +381,16 @@ def main(argv=None) -> int:
         ap.error("the following arguments are required: --out (or --video)")
     if (a.interpolate is not None) != slow_out:
         ap.error("--interpolate and a slow-motion output (--slowmo, --slowmo-video) come together")
+    if a.scale is not None and a.max_side is not None:
+        ap.error("--scale and --max-side exclude each other")
+    if (a.scale is not None and not a.scale > 0) or (a.max_side is not None and a.max_side < 1):
+        ap.error("--scale and --max-side must be positive")
     n = read_frames_and_group_predict(a.frames, a.ckpt, T=a.T, iters=a.iters, clips_per_step=a.clips_per_step, mode=a.mode,
                                       save_dir=a.out, flo_dir=a.flo, rad_max=a.rad_max, png_decode=a.png_decode,
                                       png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality, jpeg_split=a.jpeg_split,
                                       bidirectional=a.bidirectional, occlusion_dir=a.occlusion, warp_dir=a.warp, report=a.report,
-                                      interpolate=a.interpolate, slowmo_dir=a.slowmo, slowmo_video=a.slowmo_video, corr=a.corr)
+                                      interpolate=a.interpolate, slowmo_dir=a.slowmo, slowmo_video=a.slowmo_video, corr=a.corr,
+                                      scale=a.scale, max_side=a.max_side, resize_filter=a.resize_filter)
     print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp, a.slowmo, a.slowmo_video) if d))
     return 0
 

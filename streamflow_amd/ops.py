@@ -1620,6 +1620,96 @@ def frame_interp(a: torch.Tensor, b: torch.Tensor, fwd: torch.Tensor, bwd: torch
     return out, cov, stats
 
 
+def _resize_size(size, what: str):
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{what}: size must be (h, w), got {size!r}") from None
+    if h < 1 or w < 1:
+        raise RuntimeError(f"{what}: size must be positive, got {(h, w)}")
+    return h, w
+
+
+def _resize_tables(H: int, W: int, h: int, w: int, filter: str, dev, kind: str):
+    """(bounds_x, kx, ksize_x, bounds_y, ky, ksize_y) as pointers / ints: None / 0 for an axis that has no pass.  The tensors stay
+    alive in resize.device_table's cache."""
+    from . import resize
+    bx = kx = by = ky = None
+    nx = ny = 0
+    if w != W:
+        tb, tk, nx = resize.device_table(W, w, filter, dev, kind)
+        bx, kx = tb.data_ptr(), tk.data_ptr()
+    if h != H:
+        tb, tk, ny = resize.device_table(H, h, filter, dev, kind)
+        by, ky = tb.data_ptr(), tk.data_ptr()
+    return bx, kx, nx, by, ky, ny
+
+
+@on_tensor_device
+def resize_frames(frames: torch.Tensor, size: Sequence[int], filter: str = "bilinear", channels_last: Optional[bool] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 frames resampled to size = (h, w) (sf_resize_u8: Pillow's 8-bit resampler, byte for byte what PIL.Image.resize gives
+    with the same filter): frames uint8 [n, H, W, 3] or [n, 3, H, W] on the GPU, any strides (`channels_last` decides when both
+    readings fit, default: HWC if the last dimension is 3); filter: 'box', 'bilinear', 'bicubic' or 'lanczos'.  Returns (or fills
+    `out`, contiguous) uint8 [n, h, w, 3].  The coefficient tables are built on the host once per (size pair, filter, device)
+    (resize.device_table); the workspace is allocated per call.  Enqueued on the current stream, no synchronisation."""
+    what = "resize_frames"
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise RuntimeError(f"{what}: frames must be a tensor on the GPU (got {getattr(frames, 'device', type(frames).__name__)}); "
+                           "there is no CPU fallback")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.numel() == 0:
+        raise RuntimeError(f"{what}: frames must be uint8 [n, H, W, 3] or [n, 3, H, W] (got {frames.dtype} {tuple(frames.shape)})")
+    if channels_last is None:
+        channels_last = frames.shape[3] == 3
+    H, W = (int(v) for v in (frames.shape[1:3] if channels_last else frames.shape[2:]))
+    n, dev = int(frames.shape[0]), frames.device
+    fs, rs, ps, cs = _frame_strides(frames, "frames", channels_last, (H, W), n, dev, what)
+    h, w = _resize_size(size, what)
+    shape = (n, h, w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be contiguous uint8 {shape} on {dev} (got {out.dtype} {tuple(out.shape)} on {out.device})")
+    lib = _lib.load()
+    need = int(lib.sf_resize_u8_ws_bytes(n, H, W, h, w))
+    if need < 0:
+        _lib.check(need, "sf_resize_u8_ws_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    bx, kx, nx, by, ky, ny = _resize_tables(H, W, h, w, filter, dev, "u8")
+    _lib.check(lib.sf_resize_u8(frames.data_ptr(), fs, rs, ps, cs, n, H, W, h, w, bx, kx, nx, by, ky, ny, out.data_ptr(),
+                                None if ws is None else ws.data_ptr(), need, _lib.stream()), "sf_resize_u8")
+    return out
+
+
+@on_tensor_device
+def resize_flows(flows: torch.Tensor, size: Sequence[int], filter: str = "bilinear", rescale: bool = True,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Flow fields resampled to size = (h, w) (sf_resize_f32): flows fp32 [n, 2, H, W] on the GPU with contiguous rows (views are
+    fine).  rescale=True: the values are brought to the new grid's pixels, u times w / W and v times h / H (one fp32 multiply on the
+    final store); False: plain resampling of two planes.  Returns (or fills `out`, contiguous) fp32 [n, 2, h, w].  Enqueued on the
+    current stream, no synchronisation."""
+    what = "resize_flows"
+    n, H, W = _flow_fields(flows, "flows", what)
+    dev = flows.device
+    h, w = _resize_size(size, what)
+    shape = (n, 2, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be contiguous fp32 {shape} on {dev} (got {out.dtype} {tuple(out.shape)} on {out.device})")
+    lib = _lib.load()
+    need = int(lib.sf_resize_f32_ws_bytes(n, H, W, h, w))
+    if need < 0:
+        _lib.check(need, "sf_resize_f32_ws_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    bx, kx, nx, by, ky, ny = _resize_tables(H, W, h, w, filter, dev, "f32")
+    sx, sy = (w / W, h / H) if rescale else (1.0, 1.0)
+    _lib.check(lib.sf_resize_f32(flows.data_ptr(), flows.stride(0), flows.stride(1), flows.stride(2), n, H, W, h, w, bx, kx, nx, by, ky,
+                                 ny, float(sx), float(sy), out.data_ptr(), None if ws is None else ws.data_ptr(), need, _lib.stream()),
+               "sf_resize_f32")
+    return out
+
+
 PNG_BPP = (1, 2, 3, 4, 6, 8)         # PNG filter distances sf_png_unfilter is built for: 8 / 16-bit grey, grey + alpha, RGB, RGBA
 
 

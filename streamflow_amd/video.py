@@ -257,7 +257,8 @@ class _Source:
 
 @torch.no_grad()
 def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = None, clips_per_step: int = 8, mode: str = "sintel",
-                  device=None, sink: Optional[Callable[..., None]] = None, bidirectional: bool = False):
+                  device=None, sink: Optional[Callable[..., None]] = None, bidirectional: bool = False,
+                  size: Optional[Sequence[int]] = None, frame_filter: str = "bilinear", flow_filter: str = "bilinear"):
     """Flow fields of every consecutive frame pair of a video, `clips_per_step` clips per model call.
 
     frames: a uint8 tensor / array [N, H, W, 3] or [N, 3, H, W] (HWC when both readings fit) on the host or the GPU, or a sequence
@@ -275,7 +276,13 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
     forward schedule (slot T - 2 - k of the reversed clip for slot k of the forward one).  It is not predict_video on the reversed
     video, whose clip boundaries differ when (N - 1) % (T - 1) != 0.  With `sink` the call is `sink(first_pair, fwd, bwd, frames)`:
     frames is the uint8 device tensor [k + 1, H, W, 3] of the frames first_pair .. first_pair + k (a view of the batch's frame
-    buffer).  streamflow_amd.consistency turns the two fields into occlusion masks, warped frames and a report."""
+    buffer).  streamflow_amd.consistency turns the two fields into occlusion masks, warped frames and a report.
+
+    size=(h, w): the model runs at that resolution (resize.scaled_size chooses one from a factor or a longest side).  Each batch's
+    frame buffer is resampled once with ops.resize_frames (`frame_filter`; once for both directions), the clips, the padder and the
+    model see (h, w), and the gathered flows are brought back to (H, W) with ops.resize_flows (`flow_filter`, values scaled by W / w
+    and H / h) before they are returned or handed to `sink`, which still receives the ORIGINAL frames.  None (the default): the
+    frames go through at their own size, the code above alone."""
     from . import ops
     src = _Source(frames)
     if T < 2 or T - 1 > MAX_PAIRS:
@@ -294,6 +301,9 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     H, W = src.hw
+    if size is not None:
+        return _predict_video_resized(call=batched_call(model, iters), src=src, T=T, batches=batches, dev=dev, mode=mode, sink=sink,
+                                      bidirectional=bidirectional, size=size, frame_filter=frame_filter, flow_filter=flow_filter)
     pad = InputPadder((H, W), mode=mode)._pad
     call = batched_call(model, iters)
     out = None if sink is not None else torch.empty(src.n - 1, 2, H, W, dtype=torch.float32, device=dev)
@@ -319,4 +329,46 @@ def predict_video(model: Callable, frames, T: int = 4, iters: Optional[int] = No
             if sink is not None:
                 held = buf[p_lo - frame0:p_hi + 1 - frame0]
                 sink(p_lo, got, got_b, held if channels_last else held.permute(0, 2, 3, 1))
+    return (out, out_b) if bidirectional and sink is None else out
+
+
+def _predict_video_resized(call, src, T, batches, dev, mode, sink, bidirectional, size, frame_filter, flow_filter):
+    """predict_video's loop with the model at size = (h, w): frames down (or up) once per batch, flows back to the frames' grid."""
+    from . import ops, resize
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"predict_video: size must be (h, w), got {size!r}") from None
+    if h < 1 or w < 1:
+        raise ValueError(f"predict_video: size must be positive, got {(h, w)}")
+    for f in (frame_filter, flow_filter):
+        if f not in resize.FILTERS:
+            raise ValueError(f"predict_video: filter {f!r} (one of {', '.join(resize.FILTERS)})")
+    H, W = src.hw
+    pad = InputPadder((h, w), mode=mode)._pad
+    out = None if sink is not None else torch.empty(src.n - 1, 2, H, W, dtype=torch.float32, device=dev)
+    out_b = torch.empty_like(out) if bidirectional and out is not None else None
+    with torch.cuda.device(dev):
+        for first, k, f_lo, f_hi, p_lo, p_hi in batches:
+            buf, channels_last, frame0 = src.device_frames(f_lo, f_hi, dev)
+            if src.stack is not None and src.stack.is_cuda:             # the whole video is resident: only this batch's frames
+                buf, frame0 = buf[f_lo:f_hi], f_lo
+            small = ops.resize_frames(buf, (h, w), frame_filter, channels_last=channels_last)
+            imgs = ops.frames_to_clips(small, src.n, T, first, k, pad, frame0=frame0, channels_last=True)
+            passes = [(False, out)] + ([(True, out_b)] if bidirectional else [])
+            got = []
+            for reverse, dst in passes:
+                flows = list(call(imgs.flip(1) if reverse else imgs))
+                if len(flows) != T - 1:
+                    raise RuntimeError(f"predict_video: the model returned {len(flows)} flows for {'reversed ' if reverse else ''}clips "
+                                       f"of T = {T}")
+                low = ops.clips_to_flows(flows[::-1] if reverse else flows, src.n, T, first, p_lo, p_hi - p_lo, (h, w), pad)
+                got.append(ops.resize_flows(low, (H, W), flow_filter, out=None if dst is None else dst[p_lo:p_hi]))
+            if sink is None:
+                continue
+            if not bidirectional:
+                sink(p_lo, got[0])
+            else:
+                held = buf[p_lo - frame0:p_hi + 1 - frame0]
+                sink(p_lo, got[0], got[1], held if channels_last else held.permute(0, 2, 3, 1))
     return (out, out_b) if bidirectional and sink is None else out
