@@ -199,6 +199,73 @@ def test_configurations_take_the_paths_they_are_named_for(dev):
         assert not pl["f16x3_chunked", g].flash and pl["f16x3_chunked", g].attn_rows == 100 and P % 100 != 0
 
 
+CORR_ENTRY_POINTS = {"direct": ["sf_corr_direct_pack", "sf_corr_direct_lookup"],
+                     "blocked16": ["sf_corr_build_blocked", "sf_corr_lookup_blocked"],
+                     "blocked32": ["sf_corr_build_blocked32", "sf_corr_lookup_blocked32"],
+                     "rows": ["sf_corr_build_pyramid_pitched", "sf_corr_lookup_pitched"]}
+# (form, configuration, options off their defaults, the CorrBlock of that form, grid): every form at both grids where it is reachable --
+# blocked fp16 volumes need the fp16 hand-over, so only GRID_A has them; at GRID_B the same configuration keeps row-major fp16 maps
+CORR_CASES = [("direct", "config2_fp16", {"corr_direct": True}, (torch.float16, "direct"), GRID_A),
+              ("direct", "config2_fp16", {"corr_direct": True}, (torch.float16, "direct"), GRID_B),
+              ("direct", "fp32_class", {"corr_direct": True}, (torch.float32, "direct"), GRID_B),
+              ("blocked16", "config2_fp16", {}, (torch.float16, "blocked"), GRID_A),
+              ("blocked32", "fp32_class", {}, (torch.float32, "blocked"), GRID_A),
+              ("blocked32", "fp32_class", {}, (torch.float32, "blocked"), GRID_B),
+              ("rows", "fp32", {}, (torch.float32, "rows"), GRID_A),
+              ("rows", "fp32", {}, (torch.float32, "rows"), GRID_B),
+              ("rows", "config2_fp16", {}, (torch.float16, "rows"), GRID_B)]
+
+
+@pytest.mark.parametrize("form,cfg,opt,block,grid", CORR_CASES, ids=[f"{f}-{c}-{g}" for f, c, _, _, g in CORR_CASES])
+def test_engine_and_corr_block_issue_the_correlation_calls_of_one_form(dev, monkeypatch, form, cfg, opt, block, grid):
+    """One eager forward(iters=1): of the library's sf_corr_* entry points that launch (all but the host-only sizing functions) exactly
+    the build and the lookup of the form the configuration is named for are called, once each, in that order -- and a CorrBlock of
+    the matching layout and dtype on one pair (a corr.CorrStore of that form) calls the same two."""
+    from streamflow_amd import _lib
+    from streamflow_amd.corr import CorrBlock
+    eng, x = engine(dev, cfg, **opt), features(dev, grid)
+    lib, calls = _lib.load(), []
+
+    class Recorder:
+        def __getattr__(self, name):
+            fn = getattr(lib, name)
+            return lambda *a: (calls.append(name), fn(*a))[1]
+
+    launches = lambda: [c for c in calls if c.startswith("sf_corr_") and not c.endswith(("_bytes", "_geometry"))]
+    monkeypatch.setattr(_lib, "load", lambda: Recorder())
+    ups, low = eng.forward(x[0], x[1], iters=1)
+    torch.cuda.synchronize()
+    assert launches() == CORR_ENTRY_POINTS[form]
+    assert "sf_gemm" in calls and all(bool(torch.isfinite(u).all()) for u in ups)          # (the recorder saw the rest of the forward)
+    del calls[:]
+    B, h, w = grid
+    coords = torch.stack(torch.meshgrid(torch.arange(w, device=dev), torch.arange(h, device=dev), indexing="xy")).float()
+    blk = CorrBlock(x[0][:, 0], x[0][:, 1], dtype=block[0], layout=block[1])
+    out = blk(coords[None].expand(B, 2, h, w) + 1.5)
+    torch.cuda.synchronize()
+    assert blk.store.plan.form == form and launches() == CORR_ENTRY_POINTS[form]
+    assert out.shape == (B, 324, h, w) and bool(torch.isfinite(out).all())
+    # the same store handing over fp16 k-octets only (the engine's hand-over: fp16 cells, P % 4 == 0): the wrapper's call, bit for bit
+    if blk.store.plan.f16 and form != "rows" and (h * w) % 4 == 0:
+        from streamflow_amd import ops
+        from streamflow_amd.corr import CorrPlan, CorrStore
+        f1, f2 = blk._keep
+        st = CorrStore(CorrPlan(form, True, koct_out=True), B, 1, D, h, w, dev)
+        st.build(f1.data_ptr(), f2.data_ptr(), D * h * w, 0)
+        c = ops.Planes.of((coords[None].expand(B, 2, h, w) + 1.5).contiguous())
+        got, want = (ops.new_shadow(ops.Planes.of(out), dev) for _ in range(2))
+        del calls[:]
+        st.lookup(c, got)
+        if form == "direct":
+            ops.corr_direct_lookup(st.ws, c, None, want, B, 1, D, h, w, ops.PRECISION_F16)
+        else:
+            ops.corr_lookup_blocked(st.vol, c, None, want, B, 1)
+        torch.cuda.synchronize()
+        assert launches() == 2 * CORR_ENTRY_POINTS[form][1:]
+        assert torch.equal(got.base.view(torch.int32), want.base.view(torch.int32))
+        assert bool(torch.isfinite(got.tensor().float()).all())
+
+
 # ---- A. allocation contents do not matter ----------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("grid", [GRID_A, GRID_B], ids=str)
