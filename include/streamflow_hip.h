@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_VERSION 140
+#define SF_VERSION 141
 
 enum {
     SF_OK = 0,
@@ -1407,6 +1407,100 @@ int sf_inflate(const uint8_t* in, int64_t in_bytes, const int64_t* desc, int n, 
                void* stream);
 int sf_flo5_assemble(const uint8_t* chunks, int64_t chunk_stride, int n_slots, const int32_t* grid, int n, int h, int w, int ch, int cw,
                      int cc, int shuffle, float* out, void* stream);
+
+/* ---- video stabilisation: a camera motion per flow field by reweighted least squares, frames rendered through affine maps ---------
+ * Coordinates and model.  For a field of h x w, fp32, every operation rounded on its own:
+ *     cx = (float)(w - 1) * 0.5f,  cy = (float)(h - 1) * 0.5f,  s = 2.0f / (float)max(w - 1, h - 1, 1),
+ *     xn = ((float)x - cx) * s,    yn = ((float)y - cy) * s.
+ *   A model is six numbers a0 .. a5, pixels of displacement at normalised coordinates: u ~ a0 + a1 xn + a2 yn, v ~ a3 + a4 xn + a5 yn.
+ *   kind: SF_MOTION_TRANSLATION (a1 = a2 = a4 = a5 = 0), SF_MOTION_SIMILARITY (a1 = a5, a4 = -a2), SF_MOTION_AFFINE.
+ *
+ * sf_motion_moments: one weighting pass over n fields of one size; flow planes addressed as sf_flow_consistency's fwd (strides in
+ *   floats).  Only pixels with y % step == 0 && x % step == 0 take part.  Per pixel, fp32, in this order:
+ *     valid = fabsf(u) <= max_mag && fabsf(v) <= max_mag                                                    (false for NaN)
+ *     wc    = 1 without cls; with cls (uint8 [n][h][w] dense, as sf_flow_consistency writes it) w_visible / w_occluded / w_outside where
+ *             the pixel's byte is code_visible / code_occluded / code_outside (tested in this order), 0 for any other byte
+ *     without a model  wt = wc;   with model (fp32 [n][6]) and inv_c2 (fp32 [n]), which come together:
+ *       pu = a0 + (a1 xn + a2 yn),  pv = a3 + (a4 xn + a5 yn),  ru = u - pu,  rv = v - pv,  r2 = ru ru + rv rv,  t = r2 inv_c2,
+ *       wr = t < 1 ? (1 - t) (1 - t) : 0          (Tukey's biweight; 0 for NaN),       wt = wc wr
+ *     invalid pixels: wt = 0.
+ *   NaN, Inf and huge flows are ordinary inputs with defined results (weight 0); nothing forms an address from them.
+ *   moments: fp64 [n][SF_MOT_LEN], WRITTEN (not added to).  With W = (double)wt and X, Y, U, V the doubles of xn, yn, u, v, over the
+ *   pixels with wt > 0, every product rounded on its own in fp64:
+ *     S1 = sum W,  SX = sum W X,  SY = sum W Y,  SXX = sum (W X) X,  SXY = sum (W X) Y,  SYY = sum (W Y) Y,
+ *     SU = sum W U,  SXU = sum (W X) U,  SYU = sum (W Y) U,  SV = sum W V,  SXV = sum (W X) V,  SYV = sum (W Y) V,
+ *     SQQ = sum W (U U + V V),   N = the number of those pixels (exact).
+ *   ws: sf_motion_moments_ws_bytes(n, h, w, step) bytes.  A main launch (grid: blocks per field x n) and a finish launch (a block per
+ *   field sums the per-block partials in a fixed order); no atomics; the grid depends on (n, h, w, step) alone, so repeated calls
+ *   give bitwise equal rows.
+ *
+ * sf_motion_solve: moments fp64 [n][SF_MOT_LEN] -> models, fp64, a thread per field.  With M = [S1 SX SY; SX SXX SXY; SY SXY SYY],
+ *   bu = (SU, SXU, SYU), bv = (SV, SXV, SYV):
+ *     S1 > 0 is false (NaN included): the model is zero, status SF_MOT_EMPTY, rss = 0.
+ *     TRANSLATION:  a0 = SU / S1,  a3 = SV / S1.
+ *     SIMILARITY (a1 = a5 = a, a2 = b, a4 = -b):  D = (SXX + SYY) - (SX SX + SY SY) / S1,
+ *                   a = ((SXU + SYV) - (SX SU + SY SV) / S1) / D,   b = ((SYU - SXV) - (SY SU - SX SV) / S1) / D,
+ *                   a0 = ((SU - a SX) - b SY) / S1,   a3 = ((SV + b SX) - a SY) / S1.
+ *     AFFINE:       M = L L' (Cholesky: l00 = sqrt(S1), l10 = SX / l00, l20 = SY / l00, d1 = SXX - l10 l10, l11 = sqrt(d1),
+ *                   l21 = (SXY - l20 l10) / l11, d2 = (SYY - l20 l20) - l21 l21, l22 = sqrt(d2)); (a0, a1, a2) = M^-1 bu and
+ *                   (a3, a4, a5) = M^-1 bv by forward and backward substitution with the one factor.
+ *     A pivot (D; d1, d2) that is not > 2^-40 S1: the TRANSLATION model instead, status SF_MOT_DEGENERATE.
+ *   The scale of the next round, with p = the six numbers:  rss = max(0, (SQQ - 2 p.b) + p'Mp) / S1  (p.b = a0 SU + a1 SXU + a2 SYU +
+ *   a3 SV + a4 SXV + a5 SYV; p'Mp = (a0 a1 a2) M (a0 a1 a2)' + (a3 a4 a5) M (a3 a4 a5)'),  c = max(c_floor, kappa sqrt(rss)),
+ *   inv_c2 = (float)(1 / (c c)).
+ *   Outputs per field: model64 fp64 [n][6], model32 fp32 [n][6] (the rounded copy, what a next sf_motion_moments reads), c fp64 [n],
+ *   inv_c2 fp32 [n], status int32 [n].  One launch.
+ *
+ * sf_motion_fit: the whole chain of `rounds` rounds on `stream` without host synchronisation: round 0 weighs without a model, round
+ *   r > 0 with round r - 1's fp32 model and inv_c2.  Two launches a round (the finish launch of a round also solves it).
+ *   trace: fp64 [n][rounds][SF_MOT_TRACE_LEN], written: per round the moments (SF_MOT_TRACE_MOMENTS ..), the fp64 model
+ *   (SF_MOT_TRACE_MODEL ..), c, inv_c2 (the float's value) and the status.  The last round's model is the result; the model the next
+ *   round read is the fp32 rounding of the traced one.  ws: sf_motion_fit_ws_bytes(n, h, w, step) bytes.
+ *
+ * sf_warp_affine_u8: n source frames, uint8 with 3 channels, bytes addressed as sf_warp_frames' src (byte strides >= 0: HWC, CHW and
+ *   views), rendered through inv_maps fp32 [n][6] (m0 .. m5 of frame i: output pixel -> source coordinate), fp32 in this order:
+ *     sx = m0 (float)x + (m1 (float)y + m2),   sy = m3 (float)x + (m4 (float)y + m5),
+ *     inside as in "forward-backward consistency" with (px, py) = (sx, sy).  Not inside (NaN included): the pixel counts as OUTSIDE, and
+ *       SF_BORDER_CONSTANT:  the three fill bytes;
+ *       SF_BORDER_REPLICATE: a NaN in sx or sy gives the fill bytes; else sx = fminf(fmaxf(sx, 0), (float)(w - 1)), sy likewise, and
+ *                            the pixel is sampled there.
+ *     sampled pixels: out = (uint8)floorf(sample((float)src channel) + 0.5f), sample() as there.
+ *   out uint8 [n][h][w][3] dense; outside uint32 [n], WRITTEN: the number of OUTSIDE pixels per frame.  ws:
+ *   sf_warp_affine_ws_bytes(n, h, w) bytes.  A main and a finish launch, no atomics, as above.
+ *
+ * SF_ERR_BAD_ARG before any launch for: null pointers (cls may be NULL; model without inv_c2 or the reverse); h, w <= 0, h * w >=
+ * 2^30, n outside 1 .. 65535; a flow row stride < w, a zero channel stride, negative field / byte strides; step < 1; rounds outside
+ * 1 .. SF_MOT_MAX_ROUNDS; an unknown kind or border; max_mag negative or NaN; a class weight negative, infinite or NaN; kappa negative,
+ * infinite or NaN; c_floor <= 0, infinite or NaN; fp32 / uint32 pointers not 4-byte, fp64 pointers and the moments' ws not 8-byte
+ * aligned; ws_bytes too small.  The *_ws_bytes functions return SF_ERR_BAD_ARG for n, h, w, step outside the limits. */
+enum { SF_MOTION_TRANSLATION = 0, SF_MOTION_SIMILARITY = 1, SF_MOTION_AFFINE = 2 };
+enum { SF_MOT_OK = 0, SF_MOT_DEGENERATE = 1, SF_MOT_EMPTY = 2 };
+enum {
+    SF_MOT_S1 = 0, SF_MOT_SX = 1, SF_MOT_SY = 2, SF_MOT_SXX = 3, SF_MOT_SXY = 4, SF_MOT_SYY = 5, SF_MOT_SU = 6, SF_MOT_SXU = 7,
+    SF_MOT_SYU = 8, SF_MOT_SV = 9, SF_MOT_SXV = 10, SF_MOT_SYV = 11, SF_MOT_SQQ = 12, SF_MOT_N = 13, SF_MOT_LEN = 14
+};
+enum {
+    SF_MOT_TRACE_MOMENTS = 0, SF_MOT_TRACE_MODEL = 14, SF_MOT_TRACE_C = 20, SF_MOT_TRACE_INV_C2 = 21, SF_MOT_TRACE_STATUS = 22,
+    SF_MOT_TRACE_LEN = 23
+};
+#define SF_MOT_MAX_ROUNDS 16
+enum { SF_BORDER_CONSTANT = 0, SF_BORDER_REPLICATE = 1 };
+int64_t sf_motion_moments_ws_bytes(int n, int h, int w, int step);
+int sf_motion_moments(const float* flows, int64_t field_stride, int64_t ch_stride, int64_t row_stride, int n, int h, int w,
+                      const uint8_t* cls, uint8_t code_visible, uint8_t code_occluded, uint8_t code_outside, float w_visible,
+                      float w_occluded, float w_outside, int step, float max_mag, const float* model, const float* inv_c2,
+                      double* moments, void* ws, int64_t ws_bytes, void* stream);
+int sf_motion_solve(const double* moments, int n, int kind, double kappa, double c_floor, double* model64, float* model32, double* c,
+                    float* inv_c2, int32_t* status, void* stream);
+int64_t sf_motion_fit_ws_bytes(int n, int h, int w, int step);
+int sf_motion_fit(const float* flows, int64_t field_stride, int64_t ch_stride, int64_t row_stride, int n, int h, int w,
+                  const uint8_t* cls, uint8_t code_visible, uint8_t code_occluded, uint8_t code_outside, float w_visible, float w_occluded,
+                  float w_outside, int step, float max_mag, int kind, int rounds, double kappa, double c_floor, double* trace, void* ws,
+                  int64_t ws_bytes, void* stream);
+int64_t sf_warp_affine_ws_bytes(int n, int h, int w);
+int sf_warp_affine_u8(const uint8_t* src, int64_t src_frame_stride, int64_t src_row_stride, int64_t src_px_stride, int64_t src_ch_stride,
+                      const float* inv_maps, int n, int h, int w, int border, uint8_t fill0, uint8_t fill1, uint8_t fill2, uint8_t* out,
+                      uint32_t* outside, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

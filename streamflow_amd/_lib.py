@@ -230,6 +230,15 @@ SIGNATURES = {
     "sf_flo5_encode": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
     "sf_inflate": (_i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp]),
     "sf_flo5_assemble": (_i, [_vp, _i64, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sf_motion_moments_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "sf_motion_moments": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _vp, C.c_uint8, C.c_uint8, C.c_uint8, _f, _f, _f, _i, _f, _vp, _vp, _vp,
+                               _vp, _i64, _vp]),
+    "sf_motion_solve": (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sf_motion_fit_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "sf_motion_fit": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _vp, C.c_uint8, C.c_uint8, C.c_uint8, _f, _f, _f, _i, _f, _i, _i, C.c_double,
+                           C.c_double, _vp, _vp, _i64, _vp]),
+    "sf_warp_affine_ws_bytes": (_i64, [_i, _i, _i]),
+    "sf_warp_affine_u8": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i, _i, _i, C.c_uint8, C.c_uint8, C.c_uint8, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -255,7 +264,7 @@ def load() -> C.CDLL:
             raise RuntimeError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.sf_version() < 140:
+    if lib.sf_version() < 141:
         raise RuntimeError("libstreamflow_hip.so is too old; rebuild")
     _lib = lib
     return lib

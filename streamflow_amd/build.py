@@ -22,7 +22,7 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libstreamflow_hip.so")
 ASAN_OBJ = os.path.join(CSRC, "build_asan")
 ASAN_LIB = os.path.join(HERE, "libstreamflow_hip_asan.so")
-SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "corr_direct.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip", "flow_score_batch.hip", "flow_consistency.hip", "frame_interp.hip", "resize.hip", "video_io.hip", "png_unfilter.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "flo5_encode.hip", "flo5_decode.hip"]
+SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "corr_direct.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip", "flow_score_batch.hip", "flow_consistency.hip", "frame_interp.hip", "resize.hip", "video_io.hip", "png_unfilter.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "flo5_encode.hip", "flo5_decode.hip", "stabilize.hip"]
 HEADERS = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "weight_ring.h"), os.path.join(CSRC, "gemm_epilogue.h"),
            os.path.join(CSRC, "split_operand.h"), os.path.join(CSRC, "huff_deflate.h"), os.path.join(CSRC, "inflate_core.h"), os.path.join(CSRC, "jpeg_decode_core.h"), os.path.join(CSRC, "jpeg_sync_core.h"), os.path.join(HERE, "..", "include", "streamflow_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall",
@@ -40,7 +40,8 @@ HOT_KERNELS = ("gemm_bstat", "ffn_pair_kernel", "sk_tail_kernel", "gma_flash_pip
                "inflate_kernel", "flo5_assemble_kernel",
                "jpeg_dct_kernel", "jpeg_pack_kernel", "jpeg_count_kernel", "jpeg_offsets_kernel", "jpeg_gather_kernel",
                "jpeg_entropy_kernel", "jpeg_status_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
-               "jpeg_plan_kernel", "jpeg_unstuff_kernel", "jpeg_spec_kernel", "jpeg_sync_kernel", "jpeg_write_kernel", "jpeg_dc_kernel", "jpeg_finish_kernel")
+               "jpeg_plan_kernel", "jpeg_unstuff_kernel", "jpeg_spec_kernel", "jpeg_sync_kernel", "jpeg_write_kernel", "jpeg_dc_kernel", "jpeg_finish_kernel",
+               "motion_moments_kernel", "motion_finish_kernel", "motion_solve_kernel", "warp_affine_kernel", "warp_affine_finish_kernel")
 
 
 def hipcc() -> str:

@@ -163,7 +163,9 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                   jpeg_split: str = "auto", bidirectional: bool = False, occlusion_dir: str = None,
                                   warp_dir: str = None, report: bool = False, interpolate: int = None, slowmo_dir: str = None,
                                   slowmo_video: str = None, corr: str = None, scale: float = None, max_side: int = None,
-                                  resize_filter: str = "bilinear") -> int:
+                                  resize_filter: str = "bilinear", stabilize_dir: str = None, stabilize_video: str = None,
+                                  stabilize_model: str = "similarity", smooth_sigma: float = 15.0, stabilize_zoom="auto",
+                                  stabilize_border: str = "replicate", stabilize_occlusion: bool = False) -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
     baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
@@ -190,7 +192,15 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
 
     scale / max_side (at most one of them): the model runs at resize.scaled_size(frame size, scale, max_side), the frames resampled
     on the GPU with `resize_filter` and the flows brought back to the frames' own grid (video.predict_video(..., size=...)); every
-    output keeps the original size.  Neither: the frames go through as they are."""
+    output keeps the original size.  Neither: the frames go through as they are.
+
+    stabilize_dir / stabilize_video: the video with its camera shake taken out (streamflow_amd.stabilize.stabilize_video: a
+    `stabilize_model` camera motion fitted to every flow field, the camera path smoothed with a Gaussian of `smooth_sigma` frames --
+    0 or None: tripod mode, every frame rendered where frame 0 stood --, zoom `stabilize_zoom` ("auto" or a number >= 1),
+    `stabilize_border` "replicate" or "black", `stabilize_occlusion`: occluded pixels stay out of the fit), written as
+    ``stabilize_dir/stab_%06d.png`` (where `png_encode` says) and / or as one Motion-JPEG AVI file (`fps`, `jpeg_quality`).  It is
+    a pass of its own over the frames (the model runs again, at `scale` / `max_side` when given); the other outputs are written only
+    when asked for.  With `report` one more line gives the corrections, the zoom and the inlier share."""
     import os
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
@@ -209,12 +219,17 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     model = StreamFlowT4(ckpt, corr=corr).to(device).eval()
     if (interpolate is None) != (not slowmo_dir and not slowmo_video):
         raise ValueError("read_frames_and_group_predict: `interpolate` and a slow-motion output (slowmo_dir, slowmo_video) come together")
-    bidirectional = bool(bidirectional or occlusion_dir or warp_dir or report or interpolate)
-    for d in (save_dir, flo_dir, occlusion_dir, warp_dir, slowmo_dir):
+    stabilize_out = bool(stabilize_dir or stabilize_video)
+    if stabilize_border not in ("replicate", "black"):
+        raise ValueError(f"read_frames_and_group_predict: stabilize_border {stabilize_border!r} (replicate or black)")
+    # the flow outputs' own pass: skipped when only the stabilised video is asked for
+    flow_pass = bool(save_dir or flo_dir or video_path or occlusion_dir or warp_dir or interpolate or not stabilize_out)
+    bidirectional = bool(bidirectional or occlusion_dir or warp_dir or (report and flow_pass) or interpolate)
+    for d in (save_dir, flo_dir, occlusion_dir, warp_dir, slowmo_dir, stabilize_dir):
         if d:
             os.makedirs(d, exist_ok=True)
     written = [0]
-    if video_path or slowmo_video:
+    if video_path or slowmo_video or stabilize_video:
         jpeg_gpu.quant_tables(jpeg_quality)
     writer = []                                                          # opened by the first batch, which knows the frame size
 
@@ -251,8 +266,26 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
             write_images(warped[0], warp_dir, first_pair)
 
     from . import consistency
-    reporter = consistency.ReportSink(then=then) if report else None
+    reporter = consistency.ReportSink(then=then) if report and flow_pass else None
     slow_writer = []
+    stab_writer = []
+
+    def emit_stab(first: int, images: torch.Tensor) -> None:
+        """The frames first .. of the stabilised video, device uint8 [m, H, W, 3]."""
+        from . import png_gpu
+        if stabilize_dir:
+            paths = [os.path.join(stabilize_dir, "stab_%06d.png" % (first + k)) for k in range(images.shape[0])]
+            if png_encode == "gpu":
+                png_gpu.encode_batch(images.contiguous(), paths)
+            else:
+                host = images.cpu().numpy()
+                for k, p in enumerate(paths):
+                    flow_io.write_png(p, host[k])
+        if stabilize_video:
+            if not stab_writer:
+                stab_writer.append(avi.MjpegWriter(stabilize_video, int(images.shape[2]), int(images.shape[1]), fps))
+            for blob in jpeg_gpu.encode_batch(images.contiguous(), quality=jpeg_quality):
+                stab_writer[0].add(blob)
 
     def emit_slow(first: int, images: torch.Tensor) -> None:
         """The frames first .. of the slow-motion video, device uint8 [m, H, W, 3]."""
@@ -292,8 +325,11 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
         if slow is not None:
             slow(first_pair, fwd, bwd, held)
 
+    stab = None
     try:
-        if bidirectional:
+        if not flow_pass:
+            written[0] = len(frames) - 1
+        elif bidirectional:
             video.predict_video(model, frames, T=T, iters=iters, clips_per_step=clips_per_step, mode=mode, device=device,
                                 sink=sink_both, bidirectional=True, **resized)
         else:
@@ -301,8 +337,15 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                 **resized)
         if slow is not None:
             slow.finish()
+        if stabilize_out:
+            from . import stabilize
+            stab = stabilize.stabilize_video(model, frames, emit_stab, kind=stabilize_model, sigma=smooth_sigma if smooth_sigma else None,
+                                             zoom=stabilize_zoom, border="constant" if stabilize_border == "black" else "replicate",
+                                             occlusion=stabilize_occlusion, size=resized.get("size"), T=T, iters=iters,
+                                             clips_per_step=clips_per_step, mode=mode, device=device,
+                                             **{k: v for k, v in resized.items() if k != "size"})
     finally:
-        for wr in writer + slow_writer:
+        for wr in writer + slow_writer + stab_writer:
             wr.close()
     if reporter is not None:
         rep = reporter.report()
@@ -310,6 +353,8 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
             print(consistency.report_line(name, rep[name]))
         if slow is not None:
             print(interp.report_line(slow.report()))
+    if report and stab is not None:
+        print(stab.report_line())
     return written[0]
 
 
@@ -362,6 +407,31 @@ def arg_parser():
     ap.add_argument("--slowmo", default=None, metavar="DIR", help="directory for the frames of the slow-motion video, slow_%%06d.png")
     ap.add_argument("--slowmo-video", default=None, metavar="FILE.avi",
                     help="the slow-motion video as one Motion-JPEG AVI file (--fps, --jpeg-quality), encoded on the GPU")
+    ap.add_argument("--stabilize", default=None, metavar="DIR", help="directory for the frames of the stabilised video, stab_%%06d.png")
+    ap.add_argument("--stabilize-video", default=None, metavar="FILE.avi",
+                    help="the stabilised video as one Motion-JPEG AVI file (--fps, --jpeg-quality), encoded on the GPU")
+    ap.add_argument("--stabilize-model", default="similarity", choices=("translation", "similarity", "affine"),
+                    help="the camera motion fitted to every flow field")
+    ap.add_argument("--smooth-sigma", type=float, default=15.0, metavar="S",
+                    help="Gaussian smoothing of the camera path, in frames; 0: tripod mode (every frame rendered where frame 0 stood)")
+
+    def zoom(text: str):
+        if text == "auto":
+            return text
+        try:
+            value = float(text)
+        except ValueError:
+            value = 0.0
+        if not value >= 1.0:
+            raise argparse.ArgumentTypeError(f"auto or a number >= 1, got {text!r}")
+        return value
+
+    ap.add_argument("--stabilize-zoom", type=zoom, default="auto", metavar="{auto|Z}",
+                    help="zoom about the frame centre that hides the moving border: auto (the smallest that does, at most 1.25) or Z >= 1")
+    ap.add_argument("--stabilize-border", default="replicate", choices=("replicate", "black"),
+                    help="what shows where a stabilised frame reads outside its source frame")
+    ap.add_argument("--stabilize-occlusion", action="store_true",
+                    help="keep occluded and outside pixels (forward-backward consistency) out of the camera fit; runs the model both ways")
     ap.add_argument("--corr", default=None, choices=("volume", "direct"),
                     help="correlation route: the all-pairs volume (default) or on-demand lookups from features (no N x N buffer)")
     ap.add_argument("--scale", type=float, default=None, metavar="S",
@@ -377,7 +447,10 @@ def main(argv=None) -> int:
     ap = arg_parser()
     a = ap.parse_args(argv)
     slow_out = bool(a.slowmo or a.slowmo_video)
-    if not a.out and not a.video and not slow_out:
+    stab_out = bool(a.stabilize or a.stabilize_video)
+    if a.smooth_sigma < 0 or a.smooth_sigma != a.smooth_sigma:
+        ap.error("--smooth-sigma must be >= 0")
+    if not a.out and not a.video and not slow_out and not stab_out:
         ap.error("the following arguments are required: --out (or --video)")
     if (a.interpolate is not None) != slow_out:
         ap.error("--interpolate and a slow-motion output (--slowmo, --slowmo-video) come together")
@@ -390,8 +463,12 @@ def main(argv=None) -> int:
                                       png_encode=a.png_encode, video_path=a.video, fps=a.fps, jpeg_quality=a.jpeg_quality, jpeg_split=a.jpeg_split,
                                       bidirectional=a.bidirectional, occlusion_dir=a.occlusion, warp_dir=a.warp, report=a.report,
                                       interpolate=a.interpolate, slowmo_dir=a.slowmo, slowmo_video=a.slowmo_video, corr=a.corr,
-                                      scale=a.scale, max_side=a.max_side, resize_filter=a.resize_filter)
-    print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp, a.slowmo, a.slowmo_video) if d))
+                                      scale=a.scale, max_side=a.max_side, resize_filter=a.resize_filter, stabilize_dir=a.stabilize,
+                                      stabilize_video=a.stabilize_video, stabilize_model=a.stabilize_model, smooth_sigma=a.smooth_sigma,
+                                      stabilize_zoom=a.stabilize_zoom, stabilize_border=a.stabilize_border,
+                                      stabilize_occlusion=a.stabilize_occlusion)
+    print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp, a.slowmo, a.slowmo_video, a.stabilize,
+                                                           a.stabilize_video) if d))
     return 0
 
 

@@ -1553,6 +1553,122 @@ def warp_frames(src: torch.Tensor, flows: torch.Tensor, cls: Optional[torch.Tens
     return out, stats
 
 
+MOTION_KINDS = {"translation": 0, "similarity": 1, "affine": 2}      # SF_MOTION_*
+BORDERS = {"constant": 0, "replicate": 1}                             # SF_BORDER_*
+MOT_LEN, MOT_TRACE_LEN, MOT_MAX_ROUNDS = 14, 23, 16                   # SF_MOT_LEN, SF_MOT_TRACE_LEN, SF_MOT_MAX_ROUNDS
+(MOT_S1, MOT_SX, MOT_SY, MOT_SXX, MOT_SXY, MOT_SYY, MOT_SU, MOT_SXU, MOT_SYU, MOT_SV, MOT_SXV, MOT_SYV, MOT_SQQ, MOT_N) = range(14)
+MOT_TRACE_MOMENTS, MOT_TRACE_MODEL, MOT_TRACE_C, MOT_TRACE_INV_C2, MOT_TRACE_STATUS = 0, 14, 20, 21, 22
+MOT_OK, MOT_DEGENERATE, MOT_EMPTY = range(3)
+
+
+def motion_to_pixels(models: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """Normalised models float64 [..., 6] (include/streamflow_hip.h, "video stabilisation") -> [..., 2, 3] with p' = M [x, y, 1] in
+    pixels: the point a pixel of the field's first frame moves to.  float64 throughout, on the models' device."""
+    m = models.to(torch.float64)
+    cx, cy, s = (w - 1) * 0.5, (h - 1) * 0.5, 2.0 / max(w - 1, h - 1, 1)
+    a0, a1, a2, a3, a4, a5 = (m[..., k] for k in range(6))
+    rows = [1.0 + a1 * s, a2 * s, a0 - (a1 * s) * cx - (a2 * s) * cy, a4 * s, 1.0 + a5 * s, a3 - (a4 * s) * cx - (a5 * s) * cy]
+    return torch.stack(rows, dim=-1).reshape(*m.shape[:-1], 2, 3)
+
+
+@on_tensor_device
+def motion_fit(flows: torch.Tensor, cls: Optional[torch.Tensor] = None, kind: str = "similarity", rounds: int = 6, step: int = 1,
+               kappa: float = 2.0, c_floor: float = 1.0, max_mag: Optional[float] = None, codes: Sequence[int] = (0, 1, 2),
+               class_weights: Sequence[float] = (1.0, 0.0, 0.0)):
+    """A global (camera) motion per flow field by iteratively reweighted least squares (sf_motion_fit: 2 * rounds launches for the
+    whole batch, no host synchronisation).  flows fp32 [n, 2, h, w] on the GPU, any views with contiguous rows.  kind: "translation",
+    "similarity" or "affine".  Round 0 is plain (class-weighted) least squares; every later round weighs a pixel by Tukey's biweight
+    of its residual against the previous model, with the scale c = max(c_floor, kappa * RMS residual of that model) in pixels.
+    cls (flow_consistency's class map for the same flows, uint8 [n, h, w] contiguous, `codes` its bytes for visible / occluded /
+    outside) gives the classes `class_weights`; step > 1 uses every step-th pixel of every step-th row; flows beyond max_mag
+    (default 4 * max(h, w)), NaN and Inf weigh nothing.
+    Returns (models float64 [n, 2, 3] on the GPU: p' = M [x, y, 1] in pixels, the point a pixel moves to; info): info["status"]
+    int32 [n] (MOT_OK, MOT_DEGENERATE: too few pixels for `kind`, a translation was fitted; MOT_EMPTY: no pixel, zero motion),
+    info["c"] float64 [n] the last scale, info["inlier_share"] float64 [n] the last round's weight sum over round 0's,
+    info["normalised"] float64 [n, 6] and info["trace"] float64 [n, rounds, MOT_TRACE_LEN], every round's moments, model and scale."""
+    what = "motion_fit"
+    if kind not in MOTION_KINDS:
+        raise ValueError(f"{what}: kind {kind!r} (one of {', '.join(MOTION_KINDS)})")
+    if not isinstance(rounds, int) or isinstance(rounds, bool) or not 1 <= rounds <= MOT_MAX_ROUNDS:
+        raise ValueError(f"{what}: rounds must be an integer 1 .. {MOT_MAX_ROUNDS}, got {rounds!r}")
+    if not isinstance(step, int) or isinstance(step, bool) or step < 1:
+        raise ValueError(f"{what}: step must be an integer >= 1, got {step!r}")
+    n, h, w = _flow_fields(flows, "flows", what)
+    dev = flows.device
+    if max_mag is None:
+        max_mag = 4.0 * max(h, w)
+    if not (kappa >= 0 and kappa < float("inf")) or not (c_floor > 0 and c_floor < float("inf")) or not max_mag >= 0:
+        raise ValueError(f"{what}: kappa must be finite and >= 0, c_floor finite and > 0, max_mag >= 0 (got {kappa}, {c_floor}, {max_mag})")
+    codes, cw = tuple(int(c) for c in codes), tuple(float(v) for v in class_weights)
+    if len(codes) != 3 or any(not 0 <= c <= 255 for c in codes):
+        raise ValueError(f"{what}: codes must be three byte values (visible, occluded, outside), got {codes}")
+    if len(cw) != 3 or any(not (0 <= v < float("inf")) for v in cw):
+        raise ValueError(f"{what}: class_weights must be three finite weights >= 0, got {cw}")
+    if cls is not None and (not isinstance(cls, torch.Tensor) or cls.device != dev or cls.dtype != torch.uint8
+                            or tuple(cls.shape) != (n, h, w) or not cls.is_contiguous()):
+        raise RuntimeError(f"{what}: cls must be contiguous uint8 [{n}, {h}, {w}] on {dev} (got {getattr(cls, 'dtype', None)} "
+                           f"{tuple(getattr(cls, 'shape', ()))} on {getattr(cls, 'device', None)}); there is no CPU fallback")
+    lib = _lib.load()
+    trace = torch.empty(n, rounds, MOT_TRACE_LEN, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(lib.sf_motion_fit_ws_bytes(n, h, w, step)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.sf_motion_fit(flows.data_ptr(), flows.stride(0), flows.stride(1), flows.stride(2), n, h, w,
+                                 None if cls is None else cls.data_ptr(), codes[0], codes[1], codes[2], cw[0], cw[1], cw[2], step,
+                                 float(max_mag), MOTION_KINDS[kind], rounds, float(kappa), float(c_floor), trace.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _lib.stream()), "sf_motion_fit")
+    last = trace[:, -1]
+    normalised = last[:, MOT_TRACE_MODEL:MOT_TRACE_MODEL + 6]
+    total = trace[:, 0, MOT_S1]
+    info = {"status": last[:, MOT_TRACE_STATUS].to(torch.int32), "c": last[:, MOT_TRACE_C],
+            "inlier_share": torch.where(total > 0, last[:, MOT_S1] / total, torch.zeros_like(total)),
+            "normalised": normalised, "trace": trace}
+    return motion_to_pixels(normalised, h, w), info
+
+
+@on_tensor_device
+def warp_affine(frames: torch.Tensor, inv_maps: torch.Tensor, border: str = "replicate", fill: Sequence[int] = (0, 0, 0),
+                out: Optional[torch.Tensor] = None, channels_last: Optional[bool] = None):
+    """Frames rendered through affine maps (sf_warp_affine_u8): frames uint8 [n, H, W, 3] or [n, 3, H, W] on the GPU, any strides
+    (`channels_last` as warp_frames); inv_maps [n, 2, 3] (or [n, 6]), any float type on any device: the source coordinate of output
+    pixel (x, y) is inv_maps[i] @ [x, y, 1] (rounded to fp32 here).  Bilinear taps rounded to nearest.  border: "replicate" clamps
+    the source coordinate to the frame, "constant" writes the three `fill` bytes outside (a NaN coordinate gets them in either mode).
+    Returns (uint8 [n, H, W, 3] -- `out` when given: contiguous, on the frames' GPU --, outside uint32-valued int32 [n]: the pixels
+    whose source lies outside the frame).  Enqueued on the current stream."""
+    what = "warp_affine"
+    if border not in BORDERS:
+        raise ValueError(f"{what}: border {border!r} (one of {', '.join(BORDERS)})")
+    fill = tuple(int(v) for v in fill)
+    if len(fill) != 3 or any(not 0 <= v <= 255 for v in fill):
+        raise ValueError(f"{what}: fill must be three byte values, got {fill}")
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+        raise RuntimeError(f"{what}: frames must be a uint8 tensor [n, H, W, 3] or [n, 3, H, W], got {type(frames).__name__} "
+                           f"{tuple(getattr(frames, 'shape', ()))}")
+    if channels_last is None:
+        channels_last = frames.shape[3] == 3
+    n = int(frames.shape[0])
+    hw = tuple(int(v) for v in (frames.shape[1:3] if channels_last else frames.shape[2:]))
+    dev = frames.device
+    s = _frame_strides(frames, "frames", channels_last, hw, n, dev, what)
+    if n < 1 or min(hw) < 1:
+        raise RuntimeError(f"{what}: no frames or empty frames {tuple(frames.shape)}")
+    maps = torch.as_tensor(inv_maps)
+    if not maps.is_floating_point() or maps.numel() != 6 * n or tuple(maps.shape) not in ((n, 2, 3), (n, 6)):
+        raise RuntimeError(f"{what}: inv_maps must be floating point [{n}, 2, 3] (got {maps.dtype} {tuple(maps.shape)})")
+    maps = maps.to(device=dev, dtype=torch.float32).contiguous()
+    h, w = hw
+    if out is None:
+        out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3)
+          or not out.is_contiguous()):
+        raise RuntimeError(f"{what}: out must be contiguous uint8 [{n}, {h}, {w}, 3] on {dev}")
+    lib = _lib.load()
+    outside = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.sf_warp_affine_ws_bytes(n, h, w)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.sf_warp_affine_u8(frames.data_ptr(), s[0], s[1], s[2], s[3], maps.data_ptr(), n, h, w, BORDERS[border], fill[0],
+                                     fill[1], fill[2], out.data_ptr(), outside.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream()),
+               "sf_warp_affine_u8")
+    return out, outside
+
+
 INTERP_LEN = 5               # SF_INTERP_LEN: doubles per stats row of frame_interp
 INTERP_PIXELS, INTERP_BOTH, INTERP_A_ONLY, INTERP_B_ONLY, INTERP_HOLES = range(5)
 INTERP_MAX_DEN = 64
