@@ -767,7 +767,13 @@ int sf_tile_blend(const float* flows, const float* weights, float* out, const Sf
  * flows [n][2][h][w] fp32 (ch0 = u, ch1 = v) -> out [n][h][w][3] uint8 (RGB, or BGR with bgr != 0), the Middlebury wheel of
  * Baker et al. with 55 entries.  Every field is normalised by its OWN maximum radius (written to rad_max_ws[n], which stays
  * readable after the call), or by fixed_rad_max when that is >= 0 (rad_max_ws may then be null and no reduction is launched).
- * At most two kernels and one memset on `stream`, no host synchronisation: safe inside graph capture.
+ * At most three kernels on `stream` (the first clears rad_max_ws), no host synchronisation: safe inside graph capture.
+ *
+ * Per-call clears, here and in every entry point below: whatever an entry point resets per call (accumulators, status and key
+ * words, the slots bits are ORed into) it resets with a KERNEL on `stream`, never with hipMemsetAsync: a memset node of a captured
+ * graph cleared only a part of its bytes from the second replay on (ROCm 7.0), a kernel node replays as captured.  "Cleared by the
+ * call itself" therefore holds eagerly, on any stream, inside a capture and on every replay; tests/test_gpu_media_state.py runs
+ * every media entry point in used buffers, on a side stream and as a replayed graph.
  *
  * Arithmetic (the reference's numpy arithmetic for float32 input, except for its libm's float32 arctan2):
  *   fp32, every operation rounded on its own, subnormals kept, correctly rounded division and square root:
@@ -984,7 +990,7 @@ int sf_warp_frames(const uint8_t* src, int64_t src_frame_stride, int64_t src_row
  *          HOLES); exact counts.
  *   ws:    sf_frame_interp_ws_bytes(n, h, w) = 2 * 4 * 8 * n * h * w bytes of accumulators (planar: uint64 [n][side][W, C0, C1,
  *          C2][h][w]) plus the per-block partial rows of the stats; cleared by the call itself, not read by later calls.
- *   Launches: a memset of the accumulators on the stream, the splat (grid: blocks per pair x n x 2 sides; a wave owns 256 consecutive
+ *   Launches: a clear of the accumulators (a kernel on the stream), the splat (grid: blocks per pair x n x 2 sides; a wave owns 256 consecutive
  *   pixels of a row, lane l the pixels l + 64 j, so for smooth flows an atomic wave-instruction covers 512 contiguous bytes; plain
  *   no-return 64-bit integer atomic adds in global memory, at most 128 added bytes per source pixel and side), the resolve (blocks
  *   per pair x n) and the stats finish (a block per pair sums the partials in a fixed order).  The grid depends on (n, h, w) alone.
@@ -1115,7 +1121,7 @@ int sf_png_unfilter(const uint8_t* scan, int64_t scan_image_stride, int n_images
  *   refuses with SF_ERR_BAD_ARG.  The bytes of a slot between the stream's end and the bound are unspecified (the call clears them
  *   itself: `out` need not be zeroed); nothing beyond the bound is written.
  * sf_png_encode_ws_bytes: the workspace (filtered scanlines, per-band tables); -1 for a refused shape or n_images.
- * One memset and four launches (filter: a wave per row; tables: a workgroup per band; offsets: a thread per image; pack: a workgroup
+ * One clear launch and four more (filter: a wave per row; tables: a workgroup per band; offsets: a thread per image; pack: a workgroup
  *   per band, bits ORed in with vector atomics); dependencies between workgroups are launch boundaries and every trip count depends
  *   on (n_images, h, w, bpp) alone.  No host synchronisation.
  *   SF_ERR_BAD_ARG before any launch for: null pointers, n_images outside 1 .. 65535, h or w < 1, a bpp outside the set, swap16 with an
@@ -1240,7 +1246,7 @@ int sf_jpeg_encode(const uint8_t* img, int64_t img_image_stride, int64_t img_row
  *     runs under the host sanitizers as csrc/host/jpeg_decode_host_main.cpp).  Two runs are bitwise equal.
  * sf_jpeg_decode_ws_bytes: the workspace (int16 coefficients [image][component][block row][block column][64], the components' uint8
  *   planes padded to whole blocks, two words per image); -1 for a refused shape or n_images.
- * One memset (the two words per image) and four launches (entropy: one wave per interval; status: a thread per image; inverse DCT: a
+ * One clear launch (the two words per image) and four more (entropy: one wave per interval; status: a thread per image; inverse DCT: a
  *   thread per block; upsampling and colour: a thread per pixel); dependencies between workgroups are launch boundaries: no flags, no
  *   spinning, no host synchronisation.
  *   SF_ERR_BAD_ARG before anything is enqueued for: null pointers, data_bytes < 0, n_intervals outside 1 .. 2^26, n_table_sets or
@@ -1306,8 +1312,8 @@ int sf_jpeg_decode(const uint8_t* data, int64_t data_bytes, const int64_t* desc,
  *   Contract.  An image's status is 0 exactly when sf_jpeg_decode's is, and then its pixels are bitwise sf_jpeg_decode's.  A nonzero word
  *     is the split route's own: sf_jpeg_decode's depends on how far its bit buffer had read ahead (a marker behind the last MCU), which is
  *     not reproduced.  Two runs are bitwise equal.
- *   Launches.  sf_jpeg_decode's memset and four launches, plus -- unless split_min_bytes > data_bytes -- three memsets (the coefficient
- *     area, since two segments may each write their own coefficients of one block; the workgroup map; the keys) and seven launches in
+ *   Launches.  sf_jpeg_decode's clear and four launches, plus -- unless split_min_bytes > data_bytes -- two clear launches (the coefficient
+ *     area, since two segments may each write their own coefficients of one block; the keys and the workgroup map, which lie side by side) and seven launches in
  *     front of the wave launch, which skips the split intervals: plan (one workgroup scans desc on the device: which intervals split,
  *     their first workgroup of 256 segment slots and their share of the unstuffed area, by exclusive scans; the host never reads desc
  *     and sizes grids and areas from the bounds data_bytes / (256 segment_bytes) + n_intervals workgroups and data_bytes + 16 n_intervals
@@ -1349,7 +1355,7 @@ int sf_jpeg_decode_split(const uint8_t* data, int64_t data_bytes, const int64_t*
  *   nblk = 4 ceil(N / SF_FLO5_BLOCK_BYTES); -1 for rows_per_chunk or w < 1 or 4 N >= 2^31.  The bytes of a slot between the stream's end
  *   and the bound are unspecified (the call clears them itself: `out` need not be zeroed); nothing beyond the bound is written.
  * sf_flo5_encode_ws_bytes: the workspace (the shuffled chunks, per-block tables); -1 for a shape or n sf_flo5_encode refuses.
- * One memset and four launches (shuffle: a thread per 4 elements; tables: a workgroup per block; offsets: a thread per chunk; pack: a
+ * One clear launch and four more (shuffle: a thread per 4 elements; tables: a workgroup per block; offsets: a thread per chunk; pack: a
  *   workgroup per block, bits ORed in with vector atomics); dependencies between workgroups are launch boundaries and every trip
  *   count depends on (n, h, w, rows_per_chunk) alone.  No host synchronisation.
  *   SF_ERR_BAD_ARG before any launch for: null pointers, n outside 1 .. 65535, h, w or rows_per_chunk < 1, nchunks > 64 (the container

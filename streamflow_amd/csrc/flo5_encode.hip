@@ -4,7 +4,7 @@
 // such a coder can compress -- sign / exponent bytes have few values, low mantissa bytes are noise.  The format -- chunk order,
 // shuffle, blocks, table construction, header bits -- is restated in tests/flo5_encode_cases.py, and the output equals it byte for byte.
 //
-// Four launches behind one memset, every dependency between workgroups a launch boundary:
+// Four launches behind one clear launch (sf::fill_async), every dependency between workgroups a launch boundary:
 //   flo5_shuffle_kernel  a thread per 4 consecutive elements of a chunk (2 pixels x 2 channels): their bit patterns from the two
 //                        channel planes (rows past h: zero bits), one 32-bit word into each of the chunk's 4 byte planes in the
 //                        workspace.  Two floats per load where w, the strides and the base allow 8-byte loads, else float by float.
@@ -177,8 +177,8 @@ extern "C" int sf_flo5_encode(const float* flow, int64_t field_stride, int64_t c
     a.out = out, a.out_chunk_stride = out_chunk_stride, a.out_bytes = out_bytes;
     const hipStream_t s = (hipStream_t)stream;
     // the pack kernel ORs into zeroed words; nothing past sf_flo5_chunk_bound bytes of a slot is touched
-    hipError_t e = hipMemset2DAsync(out, (size_t)out_chunk_stride, 0, (size_t)bound, (size_t)a.nslots, s);
-    if (e != hipSuccess) return sf::fail(SF_ERR_HIP, "sf_flo5_encode: clearing the slots: %s", hipGetErrorString(e));
+    const int cleared = sf::fill_async("sf_flo5_encode (clearing the slots)", out, 0, bound, s, a.nslots, out_chunk_stride);
+    if (cleared != SF_OK) return cleared;
     const dim3 per_block(a.nblk, nchunks, n);
     hipLaunchKernelGGL(flo5_shuffle_kernel, dim3((unsigned)((a.plane_stride / 4 + kThreads - 1) / kThreads), nchunks, n), dim3(kThreads), 0,
                        s, a);

@@ -183,8 +183,8 @@ extern "C" int sf_flow_to_image(const float* flows, uint8_t* out, float* rad_max
     // float4 loads need 16-byte aligned planes, the dword stores 4-byte aligned images
     const bool vec = npx % 4 == 0 && (reinterpret_cast<uintptr_t>(flows) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0;
     if (!fixed) {
-        hipError_t e = hipMemsetAsync(rad_max_ws, 0, sizeof(float) * (size_t)n, s);
-        if (e != hipSuccess) return sf::fail(SF_ERR_HIP, "sf_flow_to_image: memset: %s", hipGetErrorString(e));
+        const int cleared = sf::fill_async("sf_flow_to_image (clear)", rad_max_ws, 0, (int64_t)sizeof(float) * n, s);
+        if (cleared != SF_OK) return cleared;
         // at most 256 blocks per field (one per CU): one atomic per block on the field's slot, which all XCDs share
         const dim3 grid(sf::ceil_div(ngroups, kBlock) < 256 ? sf::ceil_div(ngroups, kBlock) : 256, n);
         if (vec) hipLaunchKernelGGL(flow_rad_max_kernel<true>, grid, dim3(kBlock), 0, s, flows, rad_max_ws, npx, clip);

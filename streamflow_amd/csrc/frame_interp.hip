@@ -15,7 +15,7 @@
 // run and for any grid.  (A target that receives EVERY pixel of a 2^30-pixel field at the largest weight, importance and byte sums to
 // 2^30 * 4096 * 16 * 255 < 2^54; 32-bit fields would overflow after 255 such contributions.)
 //
-// Launches: a memset of the accumulators on the stream; splat_kernel, grid (blocks per field, n, 2 sides); resolve_kernel, grid
+// Launches: a clear of the accumulators (sf::fill_async: a kernel); splat_kernel, grid (blocks per field, n, 2 sides); resolve_kernel, grid
 // (blocks per field, n); the stats finish (a block per pair).  Accumulators are planar, uint64 [n][side][W, C0, C1, C2][h][w], and
 // both kernels use the lane mapping of flow_consistency_kernel: a wave owns 256 consecutive pixels of a row, lane l the pixels
 // l + 64 j.  For smooth flows the 64 lanes of an atomic wave-instruction then go to 64 consecutive accumulators: 512 contiguous bytes.
@@ -313,8 +313,8 @@ extern "C" int sf_frame_interp_phases(const uint8_t* a, int64_t a_frame_stride, 
     u64* acc = static_cast<u64*>(ws);
     double* partials = reinterpret_cast<double*>(static_cast<char*>(ws) + acc_bytes(n, h, w));
     if (phases & kPhaseClear) {
-        const hipError_t e = hipMemsetAsync(acc, 0, (size_t)acc_bytes(n, h, w), s);
-        if (e != hipSuccess) return sf::fail(SF_ERR_HIP, "sf_frame_interp (clear): %s", hipGetErrorString(e));
+        const int st = sf::fill_async("sf_frame_interp (clear)", acc, 0, acc_bytes(n, h, w), s);
+        if (st != SF_OK) return st;
     }
     if (phases & kPhaseSplat) {
         hipLaunchKernelGGL(splat_kernel, dim3(nblocks, n, 2), dim3(kBlock), 0, s, p, acc);

@@ -5,7 +5,7 @@
 // subset, the arithmetic and the status words are stated in include/streamflow_hip.h and restated in tests/jpeg_decode_cases.py;
 // the output equals that restatement, and libjpeg's, bit for bit.
 //
-// One memset and four launches, every dependency between workgroups a launch boundary:
+// One clear launch (sf::fill_async) and four more, every dependency between workgroups a launch boundary:
 //   jpeg_entropy_kernel  one wave per restart interval.  The decoder is csrc/jpeg_decode_core.h, the same code the sanitized host
 //                        program runs; this file adds the wave's policy.  The decode state (bit buffer, positions, symbol, DC
 //                        predictions) is the same in all 64 lanes; the lanes differ where they share work: the input window, the
@@ -27,7 +27,7 @@
 // The split route (sf_jpeg_decode_split; the functions are csrc/jpeg_sync_core.h, the same ones csrc/host/jpeg_sync_host_main.cpp
 // runs under the host sanitizers).  One wave per interval leaves a file without DRI -- one interval -- to one wave, so an interval
 // of at least split_min_bytes is decoded a THREAD per segment of segment_bytes unstuffed bytes instead, by the self-synchronising
-// method the core's header describes.  Three more memsets (the coefficient area: a block may be written by two segments, each its
+// method the core's header describes.  Two more clear launches (the coefficient area: a block may be written by two segments, each its
 // own coefficients; the workgroup map; the error keys) and seven more launches in front of jpeg_entropy_kernel, which skips the
 // intervals that split; again every dependency between workgroups is a launch boundary, there is no flag, no spinning, no host
 // synchronisation, and the only atomics are vector atomics (min on an interval's key, add / max on an image's words, an LDS min):
@@ -568,7 +568,7 @@ bool split_layout(int64_t data_bytes, int n_intervals, int segment_bytes, SplitL
     };
     L.first_wg = take(4 * (int64_t)n_intervals), L.u_off = take(8 * (int64_t)n_intervals), L.u_len = take(8 * (int64_t)n_intervals);
     L.u_err = take(4 * (int64_t)n_intervals);
-    L.err_key = take(8 * (int64_t)n_intervals), L.wg_interval = take(4 * L.wg_cap);      // adjacent: one memset of 0xFF
+    L.err_key = take(8 * (int64_t)n_intervals), L.wg_interval = take(4 * L.wg_cap);      // adjacent: one clear to 0xFF
     L.ustream = take(L.u_cap);
     L.ex_bit = take(8 * L.slots), L.ex_sk = take(4 * L.slots), L.nblk = take(4 * L.slots), L.first_blk = take(8 * L.slots);
     L.bytes = at;
@@ -654,8 +654,8 @@ extern "C" int sf_jpeg_decode(const uint8_t* data, int64_t data_bytes, const int
     a.status = status, a.out = out, a.out_image_stride = out_image_stride, a.out_row_stride = out_row_stride, a.out_channels = out_channels;
     a.split_first = nullptr;
     const hipStream_t s = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(a.first_error, 0, (size_t)n_images * 8, s);
-    if (e != hipSuccess) return sf::fail(SF_ERR_HIP, "sf_jpeg_decode: hipMemsetAsync: %s", hipGetErrorString(e));
+    const int cleared = sf::fill_async("sf_jpeg_decode (clear)", a.first_error, 0, (int64_t)n_images * 8, s);
+    if (cleared != SF_OK) return cleared;
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n_intervals), dim3(kWave), 0, s, a);
     launch_pixels(a, s);
     return sf::check_launch("sf_jpeg_decode");
@@ -690,8 +690,8 @@ extern "C" int sf_jpeg_decode_split(const uint8_t* data, int64_t data_bytes, con
     a.status = status, a.out = out, a.out_image_stride = out_image_stride, a.out_row_stride = out_row_stride, a.out_channels = out_channels;
     a.split_first = nullptr;
     const hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(a.first_error, 0, (size_t)n_images * 8, s);
-    if (e != hipSuccess) return sf::fail(SF_ERR_HIP, "sf_jpeg_decode_split: hipMemsetAsync: %s", hipGetErrorString(e));
+    int cleared = sf::fill_async("sf_jpeg_decode_split (clear)", a.first_error, 0, (int64_t)n_images * 8, s);
+    if (cleared != SF_OK) return cleared;
     if (split_min_bytes <= data_bytes) {                                // else no acceptable interval is that long: sf_jpeg_decode's launches
         SplitLayout L;
         split_layout(data_bytes, n_intervals, segment_bytes, L);
@@ -703,9 +703,9 @@ extern "C" int sf_jpeg_decode_split(const uint8_t* data, int64_t data_bytes, con
         p.ustream = x + L.ustream, p.ex_bit = reinterpret_cast<int64_t*>(x + L.ex_bit), p.ex_sk = reinterpret_cast<int32_t*>(x + L.ex_sk);
         p.nblk = reinterpret_cast<int32_t*>(x + L.nblk), p.first_blk = reinterpret_cast<int64_t*>(x + L.first_blk);
         a.split_first = p.first_wg;
-        e = hipMemsetAsync(a.coef, 0, (size_t)n_images * a.g.image_blocks * 128, s);
-        if (e == hipSuccess) e = hipMemsetAsync(p.err_key, 0xFF, (size_t)(L.ustream - L.err_key), s);
-        if (e != hipSuccess) return sf::fail(SF_ERR_HIP, "sf_jpeg_decode_split: hipMemsetAsync: %s", hipGetErrorString(e));
+        cleared = sf::fill_async("sf_jpeg_decode_split (clear)", a.coef, 0, (int64_t)n_images * a.g.image_blocks * 128, s);
+        if (cleared == SF_OK) cleared = sf::fill_async("sf_jpeg_decode_split (clear)", p.err_key, 0xFF, L.ustream - L.err_key, s);
+        if (cleared != SF_OK) return cleared;
         const dim3 seg_grid((unsigned)L.wg_cap), iv_grid((unsigned)n_intervals), tb(kSegThreads);
         hipLaunchKernelGGL(jpeg_plan_kernel, dim3(1), tb, 0, s, a, p);
         hipLaunchKernelGGL(jpeg_unstuff_kernel, iv_grid, tb, 0, s, a, p);

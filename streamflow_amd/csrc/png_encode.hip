@@ -3,7 +3,7 @@
 // device cross to the host compressed.  The host keeps the chunk framing and the CRC-32 (flow_io.png_file).  The format -- filter
 // choice, bands, table construction, header bits -- is restated in tests/png_encode_cases.py, and the output equals it byte for byte.
 //
-// Four launches behind one memset, every dependency between workgroups a launch boundary:
+// Four launches behind one clear launch (sf::fill_async), every dependency between workgroups a launch boundary:
 //   png_filter_kernel   one wave per row: the five filtered versions' sums of min(v, 256 - v), the cheapest type (ties: the lowest),
 //                       the filtered scanline into the workspace.
 //   png_table_kernel    one workgroup per band of SF_PNG_ENC_BAND_ROWS scanlines: the band's Huffman tables, its block's exact bit
@@ -184,8 +184,8 @@ extern "C" int sf_png_encode(const uint8_t* img, int64_t img_image_stride, int64
     a.out = out, a.out_image_stride = out_image_stride, a.out_bytes = out_bytes, a.n_images = n_images;
     const hipStream_t s = (hipStream_t)stream;
     // the pack kernel ORs into zeroed words; nothing past sf_png_encode_bound bytes of a slot is touched
-    hipError_t e = hipMemset2DAsync(out, (size_t)out_image_stride, 0, (size_t)bound, (size_t)n_images, s);
-    if (e != hipSuccess) return sf::fail(SF_ERR_HIP, "sf_png_encode: clearing the slots: %s", hipGetErrorString(e));
+    const int cleared = sf::fill_async("sf_png_encode (clearing the slots)", out, 0, bound, s, n_images, out_image_stride);
+    if (cleared != SF_OK) return cleared;
     const dim3 per_band(a.nbands, n_images);
     hipLaunchKernelGGL(png_filter_kernel, dim3((h + kThreads / 64 - 1) / (kThreads / 64), n_images), dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(png_table_kernel, per_band, dim3(kThreads), 0, s, a);

@@ -30,6 +30,30 @@ inline int check_launch(const char* what) {
     return SF_OK;
 }
 
+// Clearing on the stream with a KERNEL, for every word an entry point must reset per call.  hipMemsetAsync is not used for that:
+// captured into a graph it becomes a memset node, and on the ROCm 7.0 runtime a memset node clears its bytes on the first replay
+// only -- later replays leave a part of them as they were (tests/test_gpu_media_state.py: sf_frame_interp's accumulators, the
+// status words and the split tables of sf_jpeg_decode(_split) kept the previous replay's contents).  A kernel node replays as it
+// was captured.  `rows` runs of `bytes` bytes, `pitch_bytes` apart, each byte = `byte`; p, bytes and pitch_bytes multiples of 4.
+static __global__ __launch_bounds__(256) void fill_words_kernel(uint32_t* p, int64_t pitch_words, int64_t width_words, int64_t rows,
+                                                                uint32_t v) {
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+        uint32_t* row = p + r * pitch_words;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < width_words; i += (int64_t)gridDim.x * 256) row[i] = v;
+    }
+}
+inline int fill_async(const char* what, void* p, int byte, int64_t bytes, hipStream_t s, int64_t rows = 1, int64_t pitch_bytes = 0) {
+    if (bytes <= 0 || rows <= 0) return SF_OK;
+    if (((uintptr_t)p & 3) || (bytes & 3) || (pitch_bytes & 3)) return fail(SF_ERR_BAD_ARG, "%s: a clear that is no run of 32-bit words", what);
+    const int64_t words = bytes / 4;
+    const int64_t blocks = (words + 255) / 256;
+    const unsigned gx = blocks > 4096 ? 4096u : (unsigned)blocks;
+    const unsigned gy = rows > 65535 ? 65535u : (unsigned)rows;
+    const uint32_t v = 0x01010101u * (uint32_t)(byte & 255);
+    hipLaunchKernelGGL(fill_words_kernel, dim3(gx, gy), dim3(256), 0, s, static_cast<uint32_t*>(p), pitch_bytes / 4, words, rows, v);
+    return check_launch(what);
+}
+
 // erf(x) in fp32 as x*P(x^2)/Q(x^2) on [-4,4] (the rational minimax fit used by Eigen/XLA's float erf):
 // branch-free, 12 FMAs + one reciprocal; |error| <= 4.5e-7 absolute, the same class as libm erff's fp32
 // rounding.  ocml's erff has two data-dependent branches (both taken in a wave of mixed magnitudes) and made

@@ -1339,16 +1339,28 @@ def flow_score_batch(preds: Sequence[torch.Tensor], gts: Sequence[torch.Tensor],
 _NORM_LUT = {}            # device -> the normalisation table of frames_to_clips
 
 
+def refuse_first_use_in_capture(what: str, build_before: str) -> None:
+    """A device-side table cached on first use must not be built inside a graph capture: the cached tensor would belong to the graph's
+    memory pool and hold nothing until a replay, yet every later eager call would read it (the rule of _PackedStream._cached)."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what} requested for the first time inside a graph capture; build it before ({build_before})")
+
+
 def norm_lut(device) -> torch.Tensor:
     """The 256 floats a byte value maps to, built once per device ON that device with the model's own expression
     (SKFlow_MF8.forward, reference streamflow.py:102: 2 * (x / 255.0) - 1.0): whatever the device's division by a scalar rounds to,
-    the table holds exactly what the model computes from the same byte value."""
+    the table holds exactly what the model computes from the same byte value.  The first use per device must come outside a graph
+    capture (inside one it raises and caches nothing) and synchronises the stream that builds the table ONCE, so that the cached
+    table is complete for every stream that reads it afterwards; later uses enqueue nothing and wait for nothing."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"norm_lut: the table is built on the GPU it is used on (got {device}); there is no CPU fallback")
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
     if key not in _NORM_LUT:
-        _NORM_LUT[key] = (2 * (torch.arange(256, device=device).float() / 255.0) - 1.0).contiguous()
+        refuse_first_use_in_capture("norm_lut: the normalisation table", "one eager ops.norm_lut(device) or frames_to_clips call")
+        lut = (2 * (torch.arange(256, device=device).float() / 255.0) - 1.0).contiguous()
+        torch.cuda.current_stream(device).synchronize()
+        _NORM_LUT[key] = lut
     return _NORM_LUT[key]
 
 
@@ -1359,7 +1371,9 @@ def frames_to_clips(frames: torch.Tensor, n: int, T: int, first_clip: int, n_cli
     on the GPU, [n_buf, H, W, 3] or [n_buf, 3, H, W] (any strides; `channels_last` decides when both readings fit, default: HWC if
     the last dimension is 3), holding the frames frame0 .. frame0 + n_buf - 1 of a video of `n` frames; pad = [left, right, top,
     bottom] as InputPadder._pad.  Returns fp32 [n_clips, T, 3, Hp, Wp] for the clips first_clip .. first_clip + n_clips - 1 of the
-    schedule in include/streamflow_hip.h (= video.clip_count / clip_start).  Enqueued on the current stream, no synchronisation."""
+    schedule in include/streamflow_hip.h (= video.clip_count / clip_start).  Enqueued on the current stream, no synchronisation --
+    except on the FIRST use per device, which builds the normalisation table (norm_lut): that use synchronises the current stream
+    once and raises inside a graph capture, so make one eager call (or ops.norm_lut(device)) before capturing."""
     if not frames.is_cuda:
         raise RuntimeError(f"frames_to_clips: frames must be on the GPU (got {frames.device}); there is no CPU fallback")
     if frames.dtype != torch.uint8 or frames.dim() != 4:

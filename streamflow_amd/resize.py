@@ -109,7 +109,8 @@ _TABLES: Dict[tuple, tuple] = {}
 
 def device_table(in_size: int, out_size: int, filter: str, device, kind: str):
     """(bounds int32 [out, 2], k [out, ksize], ksize) on `device`, cached per (in, out, filter, device, kind); kind 'u8': k int32,
-    quantised; 'f32': k fp32, the float64 table rounded once."""
+    quantised; 'f32': k fp32, the float64 table rounded once.  The first use of a key uploads from the host, which blocks: inside a
+    graph capture it raises (and caches nothing), so call once eagerly before capturing."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"resize: the tables are used on the GPU (got {device}); there is no CPU fallback")
@@ -117,6 +118,9 @@ def device_table(in_size: int, out_size: int, filter: str, device, kind: str):
     key = (int(in_size), int(out_size), filter, index, kind)
     hit = _TABLES.get(key)
     if hit is None:
+        if torch.cuda.is_current_stream_capturing():           # the upload below blocks the host, which a capture cannot record
+            raise RuntimeError(f"resize: the {in_size} -> {out_size} {filter} table requested for the first time inside a graph "
+                               "capture; build it before (one eager call at the same sizes)")
         bounds, k = coeff_table(in_size, out_size, filter)
         if k.shape[1] > MAX_KSIZE:
             raise ValueError(f"resize: {in_size} -> {out_size} with the {filter} filter needs {k.shape[1]} taps (at most {MAX_KSIZE})")

@@ -62,7 +62,8 @@ _WEIGHTS: Dict[tuple, torch.Tensor] = {}
 
 def tile_weights(tile_hw: Sequence[int], sigma: float = TILE_SIGMA, device=None) -> torch.Tensor:
     """[th, tw] fp32 Gaussian weight patch of one crop (bitwise one ``patch_weights[i]`` of the reference's compute_weight),
-    computed on the host and cached per (tile, sigma, device)."""
+    computed on the host and cached per (tile, sigma, device).  The first use on a GPU uploads from the host, which blocks: inside a
+    graph capture it raises (and caches nothing for that device), so call once eagerly before capturing."""
     th, tw = int(tile_hw[0]), int(tile_hw[1])
     dev = torch.device("cpu") if device is None else torch.device(device)
     if dev.type == "cuda" and dev.index is None:
@@ -70,6 +71,9 @@ def tile_weights(tile_hw: Sequence[int], sigma: float = TILE_SIGMA, device=None)
     key = (th, tw, float(sigma), str(dev))
     w = _WEIGHTS.get(key)
     if w is None:
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():    # the upload blocks the host: not recordable
+            raise RuntimeError(f"tile_weights: the {th} x {tw} patch requested for the first time inside a graph capture; build it "
+                               "before (one eager tile_weights call for that device)")
         cpu_key = (th, tw, float(sigma), "cpu")
         if cpu_key not in _WEIGHTS:
             _WEIGHTS[cpu_key] = _weights_cpu(th, tw, float(sigma))
