@@ -1,4 +1,5 @@
-"""Build libstreamflow_hip.so (HIP kernels + C ABI) for gfx950 with hipcc, in-tree.
+"""Build libstreamflow_hip.so (HIP kernels + C ABI) and libstreamflow_track.so (point tracking, a library of its own) for gfx950
+with hipcc, in-tree.
 
     python -m streamflow_amd.build [--force | --clean] [--resources] [--asan]
 
@@ -25,6 +26,12 @@ ASAN_LIB = os.path.join(HERE, "libstreamflow_hip_asan.so")
 SOURCES = ["misc.hip", "corr.hip", "corr_blocked.hip", "corr_blocked32.hip", "corr_direct.hip", "conv.hip", "gemm.hip", "gemm_split.hip", "gemm_bstat.hip", "ffn_pair.hip", "sk_tail.hip", "temporal.hip", "mask_upsample.hip", "attn.hip", "encoder.hip", "tile_blend.hip", "flow_viz.hip", "flow_score.hip", "flow_score_batch.hip", "flow_consistency.hip", "frame_interp.hip", "resize.hip", "video_io.hip", "png_unfilter.hip", "png_encode.hip", "jpeg_encode.hip", "jpeg_decode.hip", "flo5_encode.hip", "flo5_decode.hip", "stabilize.hip"]
 HEADERS = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "weight_ring.h"), os.path.join(CSRC, "gemm_epilogue.h"),
            os.path.join(CSRC, "split_operand.h"), os.path.join(CSRC, "huff_deflate.h"), os.path.join(CSRC, "inflate_core.h"), os.path.join(CSRC, "jpeg_decode_core.h"), os.path.join(CSRC, "jpeg_sync_core.h"), os.path.join(HERE, "..", "include", "streamflow_hip.h")]
+# the second library (include/streamflow_track.h): its own sources, its own headers, none of the objects above; everything but its
+# sft_* entry points is hidden
+TRACK_LIB = os.path.join(HERE, "libstreamflow_track.so")
+TRACK_SOURCES = ["track.hip"]
+TRACK_HEADERS = [os.path.join(CSRC, "track_core.h"), os.path.join(HERE, "..", "include", "streamflow_track.h")]
+TRACK_FLAGS = ["-fvisibility=hidden"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function",
          # per-kernel registers / scratch / occupancy as compiler remarks: kept next to every object (<name>.res) and checked
@@ -41,7 +48,8 @@ HOT_KERNELS = ("gemm_bstat", "ffn_pair_kernel", "sk_tail_kernel", "gma_flash_pip
                "jpeg_dct_kernel", "jpeg_pack_kernel", "jpeg_count_kernel", "jpeg_offsets_kernel", "jpeg_gather_kernel",
                "jpeg_entropy_kernel", "jpeg_status_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
                "jpeg_plan_kernel", "jpeg_unstuff_kernel", "jpeg_spec_kernel", "jpeg_sync_kernel", "jpeg_write_kernel", "jpeg_dc_kernel", "jpeg_finish_kernel",
-               "motion_moments_kernel", "motion_finish_kernel", "motion_solve_kernel", "warp_affine_kernel", "warp_affine_finish_kernel")
+               "motion_moments_kernel", "motion_finish_kernel", "motion_solve_kernel", "warp_affine_kernel", "warp_affine_finish_kernel",
+               "track_advance_kernel", "track_stamp_kernel", "track_resolve_kernel", "track_clear_kernel")
 
 
 def hipcc() -> str:
@@ -84,7 +92,7 @@ def resources() -> dict:
             "Occupancy [waves/SIMD]": "occupancy", "LDS Size [bytes/block]": "lds", "VGPRs Spill": "vgpr_spill",
             "SGPRs Spill": "sgpr_spill"}
     mangled = []
-    for src in SOURCES:
+    for src in SOURCES + TRACK_SOURCES:
         path = os.path.join(OBJ, src.replace(".hip", ".res"))
         if not os.path.exists(path):
             raise RuntimeError(f"{path} missing: run streamflow_amd.build.build(force=True)")
@@ -129,8 +137,8 @@ def resources_markdown() -> str:
 
 
 def clean(asan: bool = False) -> None:
-    """Remove the objects, resource records and the shared library (the next build() starts from the sources alone)."""
-    for d, lib in ((OBJ, LIB),) + (((ASAN_OBJ, ASAN_LIB),) if asan else ()):
+    """Remove the objects, resource records and the shared libraries (the next build() starts from the sources alone)."""
+    for d, lib in ((OBJ, LIB), (OBJ, TRACK_LIB)) + (((ASAN_OBJ, ASAN_LIB),) if asan else ()):
         shutil.rmtree(d, ignore_errors=True)
         if os.path.exists(lib):
             os.remove(lib)
@@ -141,7 +149,7 @@ def compile_source(src: str, obj_dir: str, verbose: bool = False) -> str:
     build(); tests/test_abi_cpu.py compiles the smallest source this way into an empty directory."""
     os.makedirs(obj_dir, exist_ok=True)
     s, o = os.path.join(CSRC, src), os.path.join(obj_dir, src.replace(".hip", ".o"))
-    cmd = [hipcc()] + FLAGS + ["-c", s, "-o", o]
+    cmd = [hipcc()] + FLAGS + (TRACK_FLAGS if src in TRACK_SOURCES else []) + ["-c", s, "-o", o]
     if verbose:
         print("[build]", " ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -164,20 +172,27 @@ def build(force: bool = False, verbose: bool = True) -> str:
         o = os.path.join(OBJ, src.replace(".hip", ".o"))
         if force or _stale(o, [s] + HEADERS) or not os.path.exists(o[:-2] + ".res"):
             jobs.append((s, o))
+    track_jobs = []
+    for src in TRACK_SOURCES:
+        s = os.path.join(CSRC, src)
+        o = os.path.join(OBJ, src.replace(".hip", ".o"))
+        if force or _stale(o, [s] + TRACK_HEADERS) or not os.path.exists(o[:-2] + ".res"):
+            track_jobs.append((s, o))
 
     def compile_one(job):
         return compile_source(os.path.basename(job[0]), OBJ, verbose)
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        list(ex.map(compile_one, jobs))
-    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in SOURCES]
-    if force or jobs or _stale(LIB, objs):
-        cmd = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB]
-        if verbose:
-            print("[build]", " ".join(cmd), flush=True)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+        list(ex.map(compile_one, jobs + track_jobs))
+    for lib, sources, changed in ((LIB, SOURCES, jobs), (TRACK_LIB, TRACK_SOURCES, track_jobs)):
+        objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in sources]
+        if force or changed or _stale(lib, objs):
+            cmd = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", lib]
+            if verbose:
+                print("[build]", " ".join(cmd), flush=True)
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
     return LIB
 
 

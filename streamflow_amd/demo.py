@@ -165,7 +165,9 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                   slowmo_video: str = None, corr: str = None, scale: float = None, max_side: int = None,
                                   resize_filter: str = "bilinear", stabilize_dir: str = None, stabilize_video: str = None,
                                   stabilize_model: str = "similarity", smooth_sigma: float = 15.0, stabilize_zoom="auto",
-                                  stabilize_border: str = "replicate", stabilize_occlusion: bool = False) -> int:
+                                  stabilize_border: str = "replicate", stabilize_occlusion: bool = False, track: str = None,
+                                  tracks_out: str = None, track_frames_dir: str = None, track_video: str = None, track_trail: int = 16,
+                                  track_radius: int = 3, track_occlusion: bool = True) -> int:
     """The reference's `read_video_and_group_predict` + `vis_flow` (demo.py:502-548) for a directory of PNG frames, a directory of
     baseline JPEG frames or a Motion-JPEG AVI file (video.open_frames: JPEG frames are decoded on the GPU, batch by batch) ->
     StreamFlowT4(ckpt) -> video.predict_video, `clips_per_step` clips per model call, nothing kept in memory: every batch's flows
@@ -200,7 +202,14 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     `stabilize_border` "replicate" or "black", `stabilize_occlusion`: occluded pixels stay out of the fit), written as
     ``stabilize_dir/stab_%06d.png`` (where `png_encode` says) and / or as one Motion-JPEG AVI file (`fps`, `jpeg_quality`).  It is
     a pass of its own over the frames (the model runs again, at `scale` / `max_side` when given); the other outputs are written only
-    when asked for.  With `report` one more line gives the corrections, the zoom and the inlier share."""
+    when asked for.  With `report` one more line gives the corrections, the zoom and the inlier share.
+
+    track: point tracking (streamflow_amd.track): "grid:STEP" or a file of queries (`t x y` per line, or .npy); the tracks go to
+    `tracks_out` (.npz with xy [N, P, 2], status [N, P], queries [P, 3]) and / or are drawn on the frames, written as
+    ``track_frames_dir/track_%06d.png`` and / or one Motion-JPEG AVI file `track_video` (`track_trail` frames of trail, head radius
+    `track_radius`).  track_occlusion (the default) runs the model both ways and marks occluded points; False: forward only.  Like
+    the stabilised video it is a pass of its own (at `scale` / `max_side` when given; the tracks are in original pixels).  With
+    `report` one more line gives the shares of visible, occluded and lost points at the last frame and the median track length."""
     import os
     from . import avi, flow_io, jpeg_gpu, video
     from .model import StreamFlowT4
@@ -220,16 +229,19 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
     if (interpolate is None) != (not slowmo_dir and not slowmo_video):
         raise ValueError("read_frames_and_group_predict: `interpolate` and a slow-motion output (slowmo_dir, slowmo_video) come together")
     stabilize_out = bool(stabilize_dir or stabilize_video)
+    track_out = bool(tracks_out or track_frames_dir or track_video)
+    if (track is not None) != track_out:
+        raise ValueError("read_frames_and_group_predict: `track` and a track output (tracks_out, track_frames_dir, track_video) come together")
     if stabilize_border not in ("replicate", "black"):
         raise ValueError(f"read_frames_and_group_predict: stabilize_border {stabilize_border!r} (replicate or black)")
     # the flow outputs' own pass: skipped when only the stabilised video is asked for
-    flow_pass = bool(save_dir or flo_dir or video_path or occlusion_dir or warp_dir or interpolate or not stabilize_out)
+    flow_pass = bool(save_dir or flo_dir or video_path or occlusion_dir or warp_dir or interpolate or not (stabilize_out or track_out))
     bidirectional = bool(bidirectional or occlusion_dir or warp_dir or (report and flow_pass) or interpolate)
-    for d in (save_dir, flo_dir, occlusion_dir, warp_dir, slowmo_dir, stabilize_dir):
+    for d in (save_dir, flo_dir, occlusion_dir, warp_dir, slowmo_dir, stabilize_dir, track_frames_dir):
         if d:
             os.makedirs(d, exist_ok=True)
     written = [0]
-    if video_path or slowmo_video or stabilize_video:
+    if video_path or slowmo_video or stabilize_video or track_video:
         jpeg_gpu.quant_tables(jpeg_quality)
     writer = []                                                          # opened by the first batch, which knows the frame size
 
@@ -287,6 +299,25 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
             for blob in jpeg_gpu.encode_batch(images.contiguous(), quality=jpeg_quality):
                 stab_writer[0].add(blob)
 
+    track_writer = []
+
+    def emit_track(first: int, images: torch.Tensor) -> None:
+        """The frames first .. of the video with the tracks drawn, device uint8 [m, H, W, 3]."""
+        from . import png_gpu
+        if track_frames_dir:
+            paths = [os.path.join(track_frames_dir, "track_%06d.png" % (first + k)) for k in range(images.shape[0])]
+            if png_encode == "gpu":
+                png_gpu.encode_batch(images.contiguous(), paths)
+            else:
+                host = images.cpu().numpy()
+                for k, p in enumerate(paths):
+                    flow_io.write_png(p, host[k])
+        if track_video:
+            if not track_writer:
+                track_writer.append(avi.MjpegWriter(track_video, int(images.shape[2]), int(images.shape[1]), fps))
+            for blob in jpeg_gpu.encode_batch(images.contiguous(), quality=jpeg_quality):
+                track_writer[0].add(blob)
+
     def emit_slow(first: int, images: torch.Tensor) -> None:
         """The frames first .. of the slow-motion video, device uint8 [m, H, W, 3]."""
         from . import png_gpu
@@ -325,7 +356,7 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
         if slow is not None:
             slow(first_pair, fwd, bwd, held)
 
-    stab = None
+    stab = tracks = None
     try:
         if not flow_pass:
             written[0] = len(frames) - 1
@@ -344,8 +375,17 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
                                              occlusion=stabilize_occlusion, size=resized.get("size"), T=T, iters=iters,
                                              clips_per_step=clips_per_step, mode=mode, device=device,
                                              **{k: v for k, v in resized.items() if k != "size"})
+        if track is not None:
+            from . import track as trk
+            tracks = trk.track_points(model, frames, trk.parse_track_arg(track, frames.hw), T=T, iters=iters, clips_per_step=clips_per_step,
+                                      occlusion=track_occlusion, mode=mode, device=device, **resized)
+            if tracks_out:
+                tracks.save(tracks_out)
+            if track_frames_dir or track_video:
+                trk.draw_video(frames, tracks, emit_track, trail=track_trail, radius=track_radius, device=device,
+                               frames_per_step=max(1, int(clips_per_step) * (T - 1)))
     finally:
-        for wr in writer + slow_writer + stab_writer:
+        for wr in writer + slow_writer + stab_writer + track_writer:
             wr.close()
     if reporter is not None:
         rep = reporter.report()
@@ -355,6 +395,8 @@ def read_frames_and_group_predict(path: str, ckpt, T: int = 4, iters: int = 15, 
             print(interp.report_line(slow.report()))
     if report and stab is not None:
         print(stab.report_line())
+    if report and tracks is not None:
+        print(tracks.report_line())
     return written[0]
 
 
@@ -365,7 +407,8 @@ def arg_parser():
                                              "video and .flo files")
     ap.add_argument("--frames", required=True, help="directory of PNG frames or of baseline JPEG frames (sorted by name), or a Motion-JPEG .avi file")
     ap.add_argument("--ckpt", required=True, help="StreamFlow checkpoint")
-    ap.add_argument("--out", default=None, help="directory for frame_%%04d.png (may be left out only with --video or a slow-motion output)")
+    ap.add_argument("--out", default=None,
+                    help="directory for frame_%%04d.png (may be left out only with --video, a slow-motion, a stabilised or a track output)")
     ap.add_argument("--video", default=None, help="one Motion-JPEG AVI file of the colour-wheel images, encoded on the GPU")
     ap.add_argument("--fps", type=float, default=8, help="frames per second of --video")
     ap.add_argument("--jpeg-quality", type=int, default=90, help="IJG quality 1 .. 100 of the frames of --video")
@@ -432,6 +475,17 @@ def arg_parser():
                     help="what shows where a stabilised frame reads outside its source frame")
     ap.add_argument("--stabilize-occlusion", action="store_true",
                     help="keep occluded and outside pixels (forward-backward consistency) out of the camera fit; runs the model both ways")
+    ap.add_argument("--track", default=None, metavar="{grid:STEP|FILE}",
+                    help="track points through the video: a grid of spacing STEP pixels starting at frame 0, or a file of queries "
+                         "(`t x y` per line, or .npy [P, 3]); needs --tracks-out, --track-frames and / or --track-video")
+    ap.add_argument("--tracks-out", default=None, metavar="FILE.npz", help="the tracks: arrays xy [N, P, 2], status [N, P], queries [P, 3]")
+    ap.add_argument("--track-frames", default=None, metavar="DIR", help="directory for the frames with the tracks drawn, track_%%06d.png")
+    ap.add_argument("--track-video", default=None, metavar="FILE.avi",
+                    help="the frames with the tracks drawn as one Motion-JPEG AVI file (--fps, --jpeg-quality), encoded on the GPU")
+    ap.add_argument("--track-trail", type=int, default=16, metavar="N", help="frames of trail drawn behind every point (1 .. 255)")
+    ap.add_argument("--track-radius", type=int, default=3, metavar="R", help="radius of the disc at a point's newest position (0 .. 16)")
+    ap.add_argument("--no-track-occlusion", action="store_true",
+                    help="track forward only: one model call per batch instead of two, no occluded status")
     ap.add_argument("--corr", default=None, choices=("volume", "direct"),
                     help="correlation route: the all-pairs volume (default) or on-demand lookups from features (no N x N buffer)")
     ap.add_argument("--scale", type=float, default=None, metavar="S",
@@ -450,7 +504,12 @@ def main(argv=None) -> int:
     stab_out = bool(a.stabilize or a.stabilize_video)
     if a.smooth_sigma < 0 or a.smooth_sigma != a.smooth_sigma:
         ap.error("--smooth-sigma must be >= 0")
-    if not a.out and not a.video and not slow_out and not stab_out:
+    track_out = bool(a.tracks_out or a.track_frames or a.track_video)
+    if (a.track is not None) != track_out:
+        ap.error("--track and a track output (--tracks-out, --track-frames, --track-video) come together")
+    if not 1 <= a.track_trail <= 255 or not 0 <= a.track_radius <= 16:
+        ap.error("--track-trail must be 1 .. 255 and --track-radius 0 .. 16")
+    if not a.out and not a.video and not slow_out and not stab_out and not track_out:
         ap.error("the following arguments are required: --out (or --video)")
     if (a.interpolate is not None) != slow_out:
         ap.error("--interpolate and a slow-motion output (--slowmo, --slowmo-video) come together")
@@ -466,9 +525,11 @@ def main(argv=None) -> int:
                                       scale=a.scale, max_side=a.max_side, resize_filter=a.resize_filter, stabilize_dir=a.stabilize,
                                       stabilize_video=a.stabilize_video, stabilize_model=a.stabilize_model, smooth_sigma=a.smooth_sigma,
                                       stabilize_zoom=a.stabilize_zoom, stabilize_border=a.stabilize_border,
-                                      stabilize_occlusion=a.stabilize_occlusion)
+                                      stabilize_occlusion=a.stabilize_occlusion, track=a.track, tracks_out=a.tracks_out,
+                                      track_frames_dir=a.track_frames, track_video=a.track_video, track_trail=a.track_trail,
+                                      track_radius=a.track_radius, track_occlusion=not a.no_track_occlusion)
     print(f"{n} flow fields -> " + ", ".join(d for d in (a.out, a.video, a.flo, a.occlusion, a.warp, a.slowmo, a.slowmo_video, a.stabilize,
-                                                           a.stabilize_video) if d))
+                                                           a.stabilize_video, a.tracks_out, a.track_frames, a.track_video) if d))
     return 0
 
 

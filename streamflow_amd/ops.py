@@ -2322,3 +2322,113 @@ def bilinear_sampler(img: torch.Tensor, coords: torch.Tensor, want_mask: bool = 
                                                None if mask is None else mask.data_ptr(), M, Cc, Hi, Wi, Ho, Wo,
                                                _lib.stream()), "sf_bilinear_sampler")
     return (out, mask) if want_mask else out
+
+
+# ---- point tracking (libstreamflow_track, include/streamflow_track.h) ------------------------------------------------------------
+TRACK_VISIBLE, TRACK_OCCLUDED, TRACK_LOST, TRACK_PENDING = range(4)      # SFT_VISIBLE ... SFT_PENDING
+TRACK_ALPHA, TRACK_BETA = 0.01, 0.5                                      # consistency.ALPHA, consistency.BETA
+
+
+@on_tensor_device
+def track_advance(fwd: torch.Tensor, bwd: Optional[torch.Tensor] = None, state=None, start: Optional[torch.Tensor] = None,
+                  frame0: int = 0, alpha: float = TRACK_ALPHA, beta: float = TRACK_BETA, sticky: bool = False, counts: bool = False):
+    """P points through K flow fields in one launch (sft_track_advance): p <- p + bilinear(fwd_k, p) per step, with a visibility
+    decision from bwd when it is given.  fwd, bwd fp32 [K, 2, h, w] on one GPU, any views with contiguous rows (slices of
+    predict_video's outputs need no copy); field k is the pair (frame0 + k, frame0 + k + 1).  state = (xy fp32 [2, P] contiguous,
+    status uint8 [P]) as a previous call returned it, or as track.TrackSink builds it (queries, all TRACK_PENDING); None: dense mode,
+    a point per pixel of the grid, all started.  start int32 [P]: the frame at which each point becomes active (None: at once).
+    Returns (xy fp32 [K, 2, P], status uint8 [K, P], new_state): row k describes frame frame0 + k + 1; new_state is the last row
+    (views, no copy).  counts=True: a fourth result, int32 [K, 4], the points of each status per row.  Enqueued on the current
+    stream, no synchronisation."""
+    from . import _track_lib
+    what = "track_advance"
+    K, h, w = _flow_fields(fwd, "fwd", what)
+    dev = fwd.device
+    if bwd is not None and (_flow_fields(bwd, "bwd", what) != (K, h, w) or bwd.device != dev):
+        raise RuntimeError(f"{what}: fwd is {tuple(fwd.shape)} on {dev}, bwd {tuple(bwd.shape)} on {bwd.device}")
+    if min(fwd.stride(0), fwd.stride(1)) < 1 or (bwd is not None and min(bwd.stride(0), bwd.stride(1)) < 1):
+        raise RuntimeError(f"{what}: field and channel strides must be positive (fwd {fwd.stride()}, bwd {None if bwd is None else bwd.stride()})")
+    if alpha != alpha or beta != beta:
+        raise RuntimeError(f"{what}: alpha / beta is NaN")
+    sxy = sst = None
+    if state is None:
+        P = h * w
+        if start is not None:
+            raise RuntimeError(f"{what}: dense mode (state=None) starts every point at once; `start` needs a state")
+    else:
+        sxy, sst = state
+        for t, name, dt in ((sxy, "state xy", torch.float32), (sst, "state status", torch.uint8)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous():
+                raise RuntimeError(f"{what}: {name} must be a contiguous {dt} tensor on {dev} (got {getattr(t, 'dtype', type(t).__name__)} on "
+                                   f"{getattr(t, 'device', None)}); there is no CPU fallback")
+        if sxy.dim() != 2 or sxy.shape[0] != 2 or sxy.shape[1] < 1 or tuple(sst.shape) != (sxy.shape[1],):
+            raise RuntimeError(f"{what}: state must be (xy [2, P], status [P]), got {tuple(sxy.shape)} and {tuple(sst.shape)}")
+        P = int(sxy.shape[1])
+        if start is not None and (not isinstance(start, torch.Tensor) or start.device != dev or start.dtype != torch.int32
+                                  or tuple(start.shape) != (P,) or not start.is_contiguous()):
+            raise RuntimeError(f"{what}: start must be contiguous int32 [{P}] on {dev} (got {getattr(start, 'dtype', None)} "
+                               f"{tuple(getattr(start, 'shape', ()))})")
+    lib = _track_lib.load()
+    xy = torch.empty(K, 2, P, dtype=torch.float32, device=dev)
+    status = torch.empty(K, P, dtype=torch.uint8, device=dev)
+    cnt = torch.empty(K, 4, dtype=torch.int32, device=dev) if counts else None
+    b = bwd if bwd is not None else fwd
+    _track_lib.check(lib.sft_track_advance(fwd.data_ptr(), fwd.stride(0), fwd.stride(1), fwd.stride(2),
+                                           None if bwd is None else bwd.data_ptr(), b.stride(0), b.stride(1), b.stride(2), K, h, w,
+                                           int(frame0), None if sxy is None else sxy.data_ptr(), None if sst is None else sst.data_ptr(),
+                                           None if start is None else start.data_ptr(), P, float(alpha), float(beta), int(bool(sticky)),
+                                           xy.data_ptr(), status.data_ptr(), None, None, None if cnt is None else cnt.data_ptr(), None, 0,
+                                           _track_lib.stream()), "sft_track_advance")
+    new_state = (xy[K - 1], status[K - 1])
+    return (xy, status, new_state, cnt) if counts else (xy, status, new_state)
+
+
+@on_tensor_device
+def draw_tracks(frames: torch.Tensor, xy: torch.Tensor, status: torch.Tensor, first_frame: int, trail: int = 16, radius: int = 3,
+                trail_radius: int = 1, palette: Optional[torch.Tensor] = None, draw_occluded: bool = False, first_row: int = 0,
+                alpha_table: Optional[torch.Tensor] = None, channels_last: Optional[bool] = None) -> torch.Tensor:
+    """Tracks drawn on frames (sft_draw_tracks: a key image per frame, atomic maxima, then a blend; bitwise reproducible).  frames
+    uint8 [n, H, W, 3] or [n, 3, H, W] on the GPU, any strides; frames[j] is frame first_frame + j of the video.  xy fp32 [N, 2, P],
+    status uint8 [N, P] contiguous: row r describes frame first_row + r (track_advance's rows, stacked).  Every frame shows each
+    point's last `trail` samples: a disc of `radius` at the newest, discs of `trail_radius` joined by lines behind it.  palette uint8
+    [L, 3] (default: track.default_palette), alpha_table uint8 [trail] (default: track.alpha_fade).  Returns uint8 [n, H, W, 3].
+    Enqueued on the current stream, no synchronisation."""
+    from . import _track_lib, track
+    what = "draw_tracks"
+    for t, name, dt in ((xy, "xy", torch.float32), (status, "status", torch.uint8)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be a contiguous {dt} tensor on the GPU (got {getattr(t, 'dtype', type(t).__name__)} on "
+                               f"{getattr(t, 'device', None)}); there is no CPU fallback")
+    if xy.dim() != 3 or xy.shape[1] != 2 or xy.numel() == 0 or tuple(status.shape) != (xy.shape[0], xy.shape[2]) or status.device != xy.device:
+        raise RuntimeError(f"{what}: xy must be [N, 2, P] and status [N, P] on one GPU, got {tuple(xy.shape)} and {tuple(status.shape)}")
+    dev = xy.device
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[0] < 1:
+        raise RuntimeError(f"{what}: frames must be uint8 [n, H, W, 3] or [n, 3, H, W] on the GPU")
+    if channels_last is None:
+        channels_last = frames.shape[3] == 3
+    n = int(frames.shape[0])
+    h, w = (int(v) for v in (frames.shape[1:3] if channels_last else frames.shape[2:]))
+    s = _frame_strides(frames, "frames", channels_last, (h, w), n, dev, what)
+    N, P = int(xy.shape[0]), int(xy.shape[2])
+    trail, radius, trail_radius = int(trail), int(radius), int(trail_radius)
+    if not 1 <= trail <= _track_lib.DRAW_MAX_TRAIL or not 0 <= radius <= _track_lib.DRAW_MAX_RADIUS or not 0 <= trail_radius <= _track_lib.DRAW_MAX_RADIUS:
+        raise RuntimeError(f"{what}: trail {trail} (1 .. {_track_lib.DRAW_MAX_TRAIL}), radius {radius} / trail_radius {trail_radius} "
+                           f"(0 .. {_track_lib.DRAW_MAX_RADIUS})")
+    if P > _track_lib.DRAW_MAX_POINTS:
+        raise RuntimeError(f"{what}: {P} points (at most {_track_lib.DRAW_MAX_POINTS} can be drawn)")
+    if palette is None:
+        palette = torch.from_numpy(track.default_palette()).to(dev)
+    if alpha_table is None:
+        alpha_table = torch.from_numpy(track.alpha_fade(trail)).to(dev)
+    for t, name, shape in ((palette, "palette", (-1, 3)), (alpha_table, "alpha_table", (trail,))):
+        ok = isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() > 0
+        if not ok or (name == "palette" and (t.dim() != 2 or t.shape[1] != 3)) or (name == "alpha_table" and tuple(t.shape) != shape):
+            raise RuntimeError(f"{what}: {name} must be contiguous uint8 {'[L, 3]' if name == 'palette' else [trail]} on {dev}")
+    lib = _track_lib.load()
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(lib.sft_draw_tracks_ws_bytes(n, h, w)), dtype=torch.uint8, device=dev)
+    _track_lib.check(lib.sft_draw_tracks(frames.data_ptr(), s[0], s[1], s[2], s[3], n, h, w, int(first_frame), xy.data_ptr(), status.data_ptr(),
+                                         N, P, int(first_row), trail, radius, trail_radius, int(bool(draw_occluded)), palette.data_ptr(),
+                                         int(palette.shape[0]), alpha_table.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         _track_lib.stream()), "sft_draw_tracks")
+    return out
